@@ -9,15 +9,21 @@ A *step* is one full `select all` run of the greedy loop (utmos/select.py:69-112
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W          # one rank per GPU; samples sharded over the ranks
 
-N = 1, default workload: after the headline the other single-GPU BASELINE configurations run a few timed steps each (cfg3
-`--af` float32 and the same with the reference's in-memory float64 values, cfg1 chr22-sized, one rank's share of cfg4
-for 20 iterations, cfg5's 156 GB for 10) and are attached under `also`, each with its own it/s, bytes and roofline fraction.
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last
+timed step returned (DIR/idx.npy, new_count.npy, score.npy).  Everything else it can measure or check runs only with
+`--full`: the stream calibration, the roofline pass with live PMC traffic, the CPU baselines, and the legs below.
+
+N = 1, default workload, `--full`: after the headline the other single-GPU BASELINE configurations run a few timed steps
+each (cfg3 `--af` float32 and the same with the reference's in-memory float64 values, cfg1 chr22-sized, one rank's share
+of cfg4 for 20 iterations, cfg5's 156 GB for 10) and are attached under `also`, each with its own it/s, bytes and
+roofline fraction.
 
 N > 1: the same 10M x 2,504 problem is sharded over the sample axis (strong scaling).  The line says how the shards
 met every iteration (`exchange`, `rccl_ranks`, `p2p_replica_bytes`); the headline is the default exchange (device
-mailboxes over hipIpc mappings) and the same steps are timed again with north_star's RCCL protocol (ncclAllGather
-of the records + ncclBroadcast of the winner's column) under `also_exchange`.  No torch is imported: ranks find
-each other through RANK/LOCAL_RANK/WORLD_SIZE and a rendezvous file.
+mailboxes over hipIpc mappings).  With `--full` the same steps are timed again with north_star's RCCL protocol
+(ncclAllGather of the records + ncclBroadcast of the winner's column) under `also_exchange`, and rank 0 re-runs the
+problem alone to check the rows.  No torch is imported: ranks find each other through RANK/LOCAL_RANK/WORLD_SIZE and a
+rendezvous file.
 """
 import argparse
 import json
@@ -81,8 +87,8 @@ def parse():
     p.add_argument("--rccl-leg-timeout", type=float, default=240.0,
                    help="N > 1: seconds the additional RCCL measurements may take before the line is printed without them")
     p.add_argument("--exchange", choices=["auto", "mailboxes", "rccl", "rccl-allreduce", "both"], default="both",
-                   help="N > 1: both = headline through the default exchange (mailboxes, else RCCL) and the same steps again "
-                        "through RCCL (also_exchange); auto / mailboxes / rccl = that one only")
+                   help="N > 1: both = headline through the default exchange (mailboxes, else RCCL) and, with --full, the "
+                        "same steps again through RCCL (also_exchange); auto / mailboxes / rccl = that one only")
     p.add_argument("--decr-threshold", type=float, default=0.0, help="--decremental: newly-covered word fraction below which an iteration goes decremental (0 = library default)")
     p.add_argument("--pmc-traffic", choices=["live", "recorded", "off"], default="live",
                    help="roofline.traffic: live = two rocprofv3 --pmc child runs of one step of this workload (N = 1), "
@@ -93,7 +99,18 @@ def parse():
     p.add_argument("--force-comm", action="store_true", help="initialise RCCL even with one rank (exercises the RCCL exchange)")
     p.add_argument("--force-mailboxes", action="store_true",
                    help="one rank: exchange through the device mailboxes anyway (the shard posts to and collects from itself)")
+    p.add_argument("--full", action="store_true",
+                   help="run the legs beyond the headline (calibration, roofline pass, PMC traffic, `also`, CPU baselines; "
+                        "N > 1: the RCCL legs and the single-GPU check); the --no-* flags switch single legs off again")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned to DIR/<name>.npy (float64)")
     args = p.parse_args()
+    if not args.full:
+        # a plain run is repeated for every change and measures the headline only
+        args.no_calibration = args.no_roofline_pass = args.no_also = args.no_cpu_baseline = args.no_sharded_check = True
+        args.pmc_traffic = "off"
+        if args.exchange == "both":
+            args.exchange = "auto"
     args.explicit_shape = bool(args.workload) or any(a.startswith(("--n-var", "--n-samp", "--select", "--af", "--chunk-vars",
                                                                    "--decremental", "--seed")) for a in sys.argv[1:])
     if args.workload:
@@ -148,6 +165,25 @@ def timed_steps(m, k_sel, steps, warmup, sync_max):
         loop_ms += m.stats()["loop_ms"]
     elapsed = sync_max(time.perf_counter() - t0)
     return dict(iters=iters, elapsed=elapsed, loop_ms=loop_ms, rows=rows, stats=m.stats())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rows):
+    """What a caller of the timed path receives from one step (selected sample, new variants and score per iteration)
+    as float64 arrays, DIR/<name>.npy; indices and counts are exact in float64.  Past 64 MB in all: a fixed, seeded
+    sample of the iterations, the same positions in every array, which go to positions.npy."""
+    import numpy as np
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in zip(("idx", "new_count", "score"), rows)}
+    n = len(arrays["idx"])
+    if n * 8 * len(arrays) > DUMP_LIMIT_BYTES:
+        pos = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // (8 * (len(arrays) + 1)), replace=False))
+        arrays = {name: a[pos] for name, a in arrays.items()}
+        arrays["positions"] = pos.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def roofline_pass(m, k_sel, af, rank=0):
@@ -456,6 +492,8 @@ def main():
         res = timed_steps(m, k_sel, args.steps, args.warmup, sync_max)
     st = res["stats"]
     idx, new, _ = res["rows"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["rows"])
 
     roofline = None
     if not args.no_roofline_pass and not args.decremental:   # the roofline object describes the brute-force kernel only

@@ -208,7 +208,7 @@ def test_bench_multi_rank_launch_contract_on_one_gpu(tmp_path):
                    MASTER_PORT=str(port), TMPDIR=str(tmp_path))
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(ou.ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-             "--n-var", "400000", "--n-samp", "301", "--no-cpu-baseline"],
+             "--n-var", "400000", "--n-samp", "301", "--no-cpu-baseline", "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert [p.returncode for p in procs] == [0, 0, 0], [o[1][-400:] for o in outs]
@@ -262,7 +262,7 @@ def test_bench_and_cli_under_torchrun_two_ranks(tmp_path):
     env = dict(os.environ, TMPDIR=str(tmp_path))
     port = 43500 + os.getpid() % 2000
     out = subprocess.run(launch + ["--master-port", str(port), os.path.join(ou.ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                                   "--warmup", "1", "--n-var", "300000", "--n-samp", "200", "--no-cpu-baseline"],
+                                   "--warmup", "1", "--n-var", "300000", "--n-samp", "200", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ou.ROOT)
     assert out.returncode == 0, out.stderr[-800:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -272,7 +272,7 @@ def test_bench_and_cli_under_torchrun_two_ranks(tmp_path):
     # hung" -- the launcher turns that into its own failure status; a driver can tell it from a clean run)
     out = subprocess.run(launch + ["--master-port", str(port + 2), os.path.join(ou.ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
                                    "--warmup", "0", "--n-var", "300000", "--n-samp", "200", "--no-cpu-baseline",
-                                   "--rccl-leg-timeout", "0.0001"],
+                                   "--rccl-leg-timeout", "0.0001", "--full"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ou.ROOT)
     assert out.returncode != 0 and "exitcode  : 4" in out.stderr, out.stderr[-800:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -293,7 +293,7 @@ def test_bench_line_contract_single_gpu(tmp_path):
     import subprocess
     import sys
     out = subprocess.run([sys.executable, os.path.join(ou.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n-var", "2000000",
-                          "--n-samp", "500", "--cpu-sample-vars", "20000"],
+                          "--n-samp", "500", "--cpu-sample-vars", "20000", "--full"],
                          env=dict(os.environ, TMPDIR=str(tmp_path)), capture_output=True, text=True, timeout=900, cwd=ou.ROOT)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -313,8 +313,34 @@ def test_bench_line_contract_single_gpu(tmp_path):
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == "iterations/s"
 
 
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes what the last timed step returned, equal
+    to the packed C oracle on the same seeded matrix."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from utmos_amd import device
+    n_var, n_samp = 300_000, 300
+    out = subprocess.run([sys.executable, os.path.join(ou.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n-var", str(n_var),
+                          "--n-samp", str(n_samp), "--dump-outputs", str(tmp_path / "dump")],
+                         env=dict(os.environ, TMPDIR=str(tmp_path)), capture_output=True, text=True, timeout=600, cwd=ou.ROOT)
+    assert out.returncode == 0, out.stderr[-800:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "u64" and j["higher_is_better"] is True
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["also"] is None and j["also_exchange"] is None
+    cols, _ = device.synth_host(0, n_var, n_samp, want_af=False)
+    want = ou.c_greedy(cols, n_var, np.ones(n_samp, np.uint8))
+    for name, w in zip(("idx", "new_count", "score"), want):
+        got = np.load(str(tmp_path / "dump" / (name + ".npy")))
+        assert got.dtype == np.float64 and got.tolist() == w.astype(np.float64).tolist(), name
+    assert len(want[0]) == j["config"]["iterations_per_step"] > 0
+
+
 def test_bench_default_line_carries_every_single_gpu_config(tmp_path):
-    """The driver's plain `bench.py` invocation (no shape flags): the cfg2 headline plus a few steps each of cfg3, cfg1,
+    """`bench.py --full` with no shape flags: the cfg2 headline plus a few steps each of cfg3, cfg1,
     float64 AF, one rank's share of cfg4 and cfg5 under `also`, each with its own bytes and roofline fraction."""
     import json
     import subprocess
@@ -323,7 +349,7 @@ def test_bench_default_line_carries_every_single_gpu_config(tmp_path):
     if nat.device_memory(0)[1] < 200e9:
         pytest.skip("cfg5 needs an MI355X-sized HBM")
     out = subprocess.run([sys.executable, os.path.join(ou.ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                          "--pmc-traffic", "off"], env=dict(os.environ, TMPDIR=str(tmp_path)), capture_output=True, text=True,
+                          "--pmc-traffic", "off", "--full"], env=dict(os.environ, TMPDIR=str(tmp_path)), capture_output=True, text=True,
                          timeout=900, cwd=ou.ROOT)
     assert out.returncode == 0, out.stderr[-800:]
     j = json.loads(out.stdout.strip().splitlines()[-1])

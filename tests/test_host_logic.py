@@ -203,12 +203,42 @@ def test_bench_workload_presets_and_profiler_guard(monkeypatch):
     a = bench.parse()
     assert (a.n_var, a.n_samp, a.select, a.steps, a.warmup, a.gpus) == (10_000_000, 2504, -1, 5, 2, 1)   # = cfg2
     assert bench.WORKLOADS["cfg2"][1] == dict(n_var=a.n_var, n_samp=a.n_samp, select=a.select)
-    assert not a.explicit_shape                       # the driver's plain invocation: the other configs ride along
+    assert not a.explicit_shape and not a.full and a.dump_outputs is None
+    # a plain run times the headline only; every other leg is behind --full
+    assert a.no_calibration and a.no_roofline_pass and a.no_also and a.no_cpu_baseline and a.no_sharded_check
+    assert a.pmc_traffic == "off" and a.exchange == "auto"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.explicit_shape            # the other configs ride along
+    assert not (a.no_calibration or a.no_roofline_pass or a.no_also or a.no_cpu_baseline or a.no_sharded_check)
+    assert a.pmc_traffic == "live" and a.exchange == "both"
     assert {"cfg1", "cfg3", "cfg4rank", "cfg5"} <= set(bench.ALSO) and all(n in bench.WORKLOADS for n in bench.ALSO)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--n-var", "1000"])
     assert bench.parse().explicit_shape
     monkeypatch.setenv("ROCPROFILER_TEST_MARK", "1")
     assert bench.live_pmc_traffic(bench.spec_of(a), []) is None
+
+
+def test_bench_dump_outputs_are_float64_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: the arrays one step returns, float64; past the cap a seeded sample of the same positions in each."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ou.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rows = (np.arange(100, dtype=np.int64)[::-1], np.arange(100, dtype=np.int64) * 7, np.linspace(0.5, 9.5, 100))
+    bench.dump_outputs(str(tmp_path / "all"), rows)
+    for name, want in zip(("idx", "new_count", "score"), rows):
+        got = np.load(str(tmp_path / "all" / (name + ".npy")))
+        assert got.dtype == np.float64 and got.tolist() == want.astype(np.float64).tolist()
+    assert not (tmp_path / "all" / "positions.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 4 * 10)        # room for 10 iterations of 3 arrays + positions
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), rows)
+    pos = np.load(str(tmp_path / "a" / "positions.npy")).astype(np.int64)
+    assert len(pos) == 10 and (np.diff(pos) > 0).all()
+    assert pos.tolist() == np.load(str(tmp_path / "b" / "positions.npy")).astype(np.int64).tolist()
+    for name, want in zip(("idx", "new_count", "score"), rows):
+        assert np.load(str(tmp_path / "a" / (name + ".npy"))).tolist() == want[pos].astype(np.float64).tolist()
 
 
 def test_stale_rendezvous_file_is_not_followed(tmp_path):

@@ -66,12 +66,10 @@ def test_ties_pick_lowest_index_and_excluded_never_cover():
 
 def test_fixture_provenance_static_jl_reader():
     """tests/golden/chunk*.npz are what tools/jl_static.py (opcode walk, nothing unpickled) reads out of the
-    reference's own .jl fixtures -- checked whenever the reference tree is present (build container only)."""
+    reference's own .jl fixtures (stored unchanged under tests/golden/jl)."""
     import os
     import sys
-    ref = "/root/reference/repo_utils/test_files"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present (GPU box)")
+    ref = os.path.join(ou.GOLD, "jl")
     sys.path.insert(0, os.path.join(ou.ROOT, "tools"))
     from jl_static import read_jl
     for name in ("chunk0", "chunk1", "chunk2"):

@@ -23,7 +23,7 @@ def main():
     for combo in itertools.product(*(GRID[k] for k in keys)):
         env = dict(os.environ, **dict(zip(keys, combo)))
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                              "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True)
+                              "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True)
         try:
             j = json.loads(out.stdout.strip().splitlines()[-1])
             r = j["roofline"] or {}
