@@ -40,21 +40,32 @@ static void launch_score_int(utm_ctx *c, const LaunchTimer &t, const Chunk &ch, 
 {
     const u64 *cols = ch.cols;
     const PickArgs pa = pick_args(c);
-#define UTM_LAUNCH_INT(NT, FUSED)                                                                                                  \
-    UTM_TIMED_LAUNCH(t, (k_score_int<STEPS, NT, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), cols, ch.covered, ch.wp,       \
+#define UTM_LAUNCH_K(K, NT, FUSED)                                                                                                 \
+    UTM_TIMED_LAUNCH(t, (K<STEPS, NT, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), cols, ch.covered, ch.wp,                 \
                      pending_of(c, ch, true), (const IterState *)c->d_st, (const unsigned *)c->d_act, c->d_cnt, group, n_groups,   \
                      how.by_pos ? 1u : 0u, pa)
-    if (how.fused == 2) {
-        if (nt) UTM_LAUNCH_INT(true, 2);
-        else UTM_LAUNCH_INT(false, 2);
-    } else if (how.fused == 1) {
-        if (nt) UTM_LAUNCH_INT(true, 1);
-        else UTM_LAUNCH_INT(false, 1);
-    } else {
-        if (nt) UTM_LAUNCH_INT(true, 0);
-        else UTM_LAUNCH_INT(false, 0);
+#define UTM_LAUNCH_INT(K)                                                                                                          \
+    if (how.fused == 2) {                                                                                                          \
+        if (nt) UTM_LAUNCH_K(K, true, 2);                                                                                          \
+        else UTM_LAUNCH_K(K, false, 2);                                                                                            \
+    } else if (how.fused == 1) {                                                                                                   \
+        if (nt) UTM_LAUNCH_K(K, true, 1);                                                                                          \
+        else UTM_LAUNCH_K(K, false, 1);                                                                                            \
+    } else {                                                                                                                       \
+        if (nt) UTM_LAUNCH_K(K, true, 0);                                                                                          \
+        else UTM_LAUNCH_K(K, false, 0);                                                                                            \
     }
+    // 32 and 16 KiB tiles: the register-quarter form (same unit of work, grid and arrivals) unless UTM_SCORE_FORM=0.
+    // Its short last quarter reads the column's last STEPS/4 KiB, so a column shorter than one tile keeps k_score_int.
+    if constexpr (STEPS == 32 || STEPS == 16) {
+        if (c->tune.score_form == 1 && ch.wp >= (u64)STEPS * UTM_STEP_WORDS) {
+            UTM_LAUNCH_INT(k_score_intq)
+            return;
+        }
+    }
+    UTM_LAUNCH_INT(k_score_int)
 #undef UTM_LAUNCH_INT
+#undef UTM_LAUNCH_K
 }
 
 static void launch_apply_pending(utm_ctx *c)

@@ -165,3 +165,185 @@ __global__ __launch_bounds__(256, UTM_SCORE_WAVES(STEPS)) void k_score_int(const
 #undef UTM_BATCH_LOAD
 #undef UTM_BATCH_COUNT
 }
+
+// ------------------------------------------------------------------------------------------------
+// K1, second form (register quarters): the same unit of work as k_score_int -- one (tile, sample group) per workgroup,
+// the same grid and block -> unit map -- but no LDS tile.  Wave w owns quarter w of the tile (STEPS/4 KiB): it loads
+// `covered | pending winner` for that quarter from global memory (L2: every group of the tile reads it) and keeps its
+// complement in registers, so nothing waits on a barrier before the columns stream.  Each wave then streams its
+// quarter of every sample of the group: 8 KiB pieces at 32 KiB tiles; at 16 KiB tiles the pieces are 4 KiB and two
+// samples' pieces are in flight together (P = 2), so a wave keeps ~8 KiB in flight either way.  A wave's partial
+// of a sample goes into an LDS slot; after a barrier, one lane per sample adds the four quarters and issues the
+// single atomic of that (sample, tile) -- the same arrivals as k_score_int, so the picker (fused_pick) and k_pick are
+// unchanged.  Partials are collected in rounds of UTM_Q_ROUND group positions, double buffered: one barrier a round.
+// ------------------------------------------------------------------------------------------------
+#define UTM_Q_ROUND 64
+#ifndef UTM_SCORE_Q_WAVES
+#define UTM_SCORE_Q_WAVES 6
+#endif
+template <int STEPS, bool NT, int FUSED>
+__global__ __launch_bounds__(256, UTM_SCORE_Q_WAVES) void k_score_intq(const u64 *__restrict__ cols, u64 *__restrict__ covered, u64 wp,
+                                                                     const Pending pend, const IterState *__restrict__ st,
+                                                                     const unsigned *__restrict__ act, u64 *__restrict__ cnt,
+                                                                     unsigned group_size, unsigned n_groups, unsigned by_pos,
+                                                                     const PickArgs pa)
+{
+    static_assert(STEPS == 32 || STEPS == 16, "register quarters: 32 or 16 KiB tiles");
+    constexpr int Q = STEPS / 4;             // KiB (load steps) of the tile per wave
+    constexpr int P = Q >= 8 ? 1 : 8 / Q;    // samples whose pieces are in flight together
+    __shared__ unsigned part[2][4][UTM_Q_ROUND];  // [round buffer][wave][group position - round start]
+    __shared__ IntCand pick_lds[5];               // the picker block: 4 wave bests + its two flags
+    // (the wave index through readfirstlane: what depends on it -- the quarter, its clamps -- is then known to be uniform
+    // and stays in scalar registers and scalar branches)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    unsigned tile, grp;
+    const bool has_unit = tile_of_block(wp, STEPS * UTM_STEP_WORDS, n_groups, tile, grp);
+    const unsigned lo = grp * group_size;
+    // the first two batches' samples, read ahead of the bounds that say whether they count (act[] is padded)
+    const bool in_act = has_unit && lo + 2 * P < pa.n_local + UTM_PICK_PAD;
+    unsigned s[P], s_next[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        s[q] = in_act ? act[lo + q] : 0;
+        s_next[q] = in_act ? act[lo + P + q] : 0;
+    }
+    typedef unsigned v8u __attribute__((ext_vector_type(8)));
+    v8u raw;
+    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(raw) : "s"(st) : "memory");
+    const IterHead head = __builtin_bit_cast(IterHead, raw);
+    const unsigned n_active = head.n_active;
+    if (head.done) return;
+    if (FUSED && blockIdx.x == gridDim.x - 1) {
+        const unsigned n_tiles = (unsigned)((wp + STEPS * UTM_STEP_WORDS - 1) / (STEPS * UTM_STEP_WORDS));
+        fused_pick<FUSED>(pa, n_tiles, pick_lds);
+        return;
+    }
+    if (!has_unit) return;
+    const u64 w0 = (u64)tile * STEPS * UTM_STEP_WORDS;
+    const u64 left = (wp - w0) / UTM_STEP_WORDS;
+    const int nsteps = left < (u64)STEPS ? (int)left : STEPS;
+    // this wave's steps of the tile: qn of Q (the last tile of a column may end inside a quarter, or before it)
+    const int qn = nsteps - wave * Q <= 0 ? 0 : nsteps - wave * Q < Q ? nsteps - wave * Q : Q;
+    // The window of Q steps this wave reads: its quarter, or -- a quarter cut short by the column's end -- the last Q
+    // steps of the column (the host keeps columns shorter than one tile on k_score_int, so the window starts inside
+    // the column, at worst in the previous tile).  The window's steps of other waves get ~covered = 0 and count zero:
+    // the same loads and counts as a full quarter, only the base and that mask differ (both wave-uniform).  The price:
+    // up to Q-1 KiB re-read per sample in a column's last tile (cfg2: 3 KiB per 1,221 KiB column).
+    const int q0 = qn == Q ? wave * Q : nsteps - Q;  // first step of the window, relative to the tile
+    const u64 wq = w0 + (u64)(i64)q0 * UTM_STEP_WORDS;
+    const int own0 = Q - qn;  // the window's first step of this wave's own
+    const unsigned hi = lo + group_size < n_active ? lo + group_size : n_active;
+#define UTM_COL_LOAD(ptr) (NT ? __builtin_nontemporal_load(ptr) : *(ptr))
+    // One batch = this wave's window (Q KiB) of the samples at positions I .. I+P-1.
+#define UTM_Q_BATCH_LOAD(I)                                                                                   \
+    if (qn) {                                                                                                 \
+        _Pragma("unroll") for (int q = 0; q < P; ++q) if ((I) + q < hi)                                       \
+        {                                                                                                     \
+            const v4u *p_ = reinterpret_cast<const v4u *>(cols + (u64)s[q] * wp + wq) + lane;                 \
+            _Pragma("unroll") for (int j = 0; j < Q; ++j) x[q * Q + j] = UTM_COL_LOAD(p_ + j * 64);           \
+        }                                                                                                     \
+    }
+
+    // Software pipeline: the first batch is requested before the tile quarter (at 32 KiB tiles its first half only: the
+    // whole batch, the quarter and the winner's words do not fit the registers of 6 waves/SIMD together), and the next
+    // batch before this batch's reductions and partials.
+    constexpr int PRE = Q >= 8 ? Q / 2 : P * Q;
+    v4u x[P * Q];
+    if (qn && lo < hi) {
+        const v4u *p_ = reinterpret_cast<const v4u *>(cols + (u64)s[0] * wp + wq) + lane;
+#pragma unroll
+        for (int j = 0; j < (PRE < Q ? PRE : Q); ++j) x[j] = UTM_COL_LOAD(p_ + j * 64);
+        if (P > 1 && lo + 1 < hi) {
+            p_ = reinterpret_cast<const v4u *>(cols + (u64)s[P - 1] * wp + wq) + lane;
+#pragma unroll
+            for (int j = 0; j < Q; ++j) x[(P - 1) * Q + j] = UTM_COL_LOAD(p_ + j * 64);
+        }
+    }
+
+    const v4u zero4 = {0, 0, 0, 0};
+    v4u live[Q];
+    if (qn) {
+        v4u *cv = reinterpret_cast<v4u *>(covered + wq) + lane;
+        const u64 *wcol = pend.fuse ? pending_column(&head, cols, wp, pend) : nullptr;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) live[j] = cv[j * 64];
+        if (wcol) {
+            // the winner's words in two halves (registers, as above)
+            const v4u *wc = reinterpret_cast<const v4u *>(wcol + wq) + lane;
+            constexpr int H = Q / 2;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                v4u w[H];
+#pragma unroll
+                for (int j = 0; j < H; ++j) w[j] = wc[(h * H + j) * 64];
+#pragma unroll
+                for (int j = 0; j < H; ++j) live[h * H + j] |= w[j];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // every group of this tile computes the same words; group 0 stores them.  A racing reader
+            // sees old or new words and ORs the winner in itself, so either is right.
+            if (grp == 0) {
+#pragma unroll
+                for (int j = 0; j < Q; ++j)
+                    if (j >= own0) cv[j * 64] = live[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < Q; ++j) live[j] = j >= own0 ? ~live[j] : zero4;
+    }
+    if (PRE < Q && qn && lo < hi) {
+        const v4u *p_ = reinterpret_cast<const v4u *>(cols + (u64)s[0] * wp + wq) + lane;
+#pragma unroll
+        for (int j = PRE; j < Q; ++j) x[j] = UTM_COL_LOAD(p_ + j * 64);
+    }
+
+    unsigned base = lo, buf = 0;  // the current round of partials: first group position, LDS buffer
+    for (unsigned i = lo; i < hi; i += P) {
+        unsigned acc[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            acc[q] = 0;
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                const v4u b = x[q * Q + j] & live[j];
+                acc[q] += __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+            }
+            // (the counts are made HERE: left to itself the compiler sinks them below the next batch's loads, which
+            // then need a second set of x registers -- and spill)
+            asm volatile("" : "+v"(acc[q]));
+        }
+        const unsigned nxt = i + P;
+        if (nxt < hi) {
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                s[q] = s_next[q];
+                s_next[q] = nxt + P + q < hi ? act[nxt + P + q] : 0;
+            }
+            UTM_Q_BATCH_LOAD(nxt)
+        }
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            const unsigned sum = wave_sum_u32(qn ? acc[q] : 0u);
+            if (lane == 0 && i + q < hi) part[buf][wave][i + q - base] = sum;
+        }
+        if (nxt >= hi || nxt - base == UTM_Q_ROUND) {  // (uniform over the workgroup) the round's partials are complete
+            __syncthreads();
+            const unsigned n = (nxt < hi ? nxt : hi) - base;
+            if (threadIdx.x < n) {
+                const unsigned t = threadIdx.x, pos = base + t;
+                const unsigned v = part[buf][0][t] + part[buf][1][t] + part[buf][2][t] + part[buf][3][t];
+                // FUSED: every partial arrives, a zero one too (see k_score_int)
+                if (FUSED) {
+                    const bool drop = pa.test_drop && blockIdx.x == 0 && pos == lo;  // (test hook: see PickArgs::test_drop)
+                    if (!drop) atomicAdd(&cnt[pos], (u64)v + (1ull << UTM_ARRIVAL_SHIFT));
+                } else if (v) {
+                    atomicAdd(&cnt[by_pos ? pos : act[pos]], (u64)v);
+                }
+            }
+            base = nxt;
+            buf ^= 1;
+        }
+    }
+#undef UTM_COL_LOAD
+#undef UTM_Q_BATCH_LOAD
+}

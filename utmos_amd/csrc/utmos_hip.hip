@@ -121,6 +121,7 @@ static int rccl_load()
 // utm_env_overrides() returns the same list (bench.py puts it into its JSON line).
 struct Tune {
     int target_wgs, min_wgs, min_wgs_big, tile_steps, nt_loads, nt_min_mb;  // scoring grid shape
+    int score_form;                                                          // integer scoring kernel at 32 / 16 KiB tiles
     int fuse_pick, pick_threads, batch;                                      // pick placement, host sync distance
     int af_steps, af_target_wgs, af_tables, af_table_run, af_table_wgs_per_cu, chain_pick, af_verify, af_record, af_defer; // AF kernels
     double af_switch, af_dense_delta;
@@ -144,6 +145,7 @@ static const KnobDef g_knobs[] = {
     UTM_KNOB_I("UTM_TILE_STEPS", tile_steps, 0),
     UTM_KNOB_I("UTM_NT_LOADS", nt_loads, -1),
     UTM_KNOB_I("UTM_NT_MIN_MB", nt_min_mb, 512),
+    UTM_KNOB_I("UTM_SCORE_FORM", score_form, 1),      // integer launches at 32 / 16 KiB tiles: 0 = k_score_int (LDS tile), 1 = k_score_intq (tile quarters in registers)
     UTM_KNOB_I("UTM_FUSE_PICK", fuse_pick, 1),
     UTM_KNOB_I("UTM_PICK_THREADS", pick_threads, 0),
     UTM_KNOB_I("UTM_BATCH", batch, 0),
