@@ -288,6 +288,35 @@ int utm_comm_allreduce_max(utm_ctx *ctx, double *value); /* in place; also a bar
  * enqueued in batches like on one GPU).  Same rows either way. */
 int utm_comm_column_by_allreduce(utm_ctx *ctx, int32_t on);
 
+/* ---- VCF genotype parsing (no utm_ctx) ---------------------------------------------------------- */
+/* The genotype half of the reference's `convert` (utmos/convert.py:43-88; utmos_amd/vcfio.py restates it on the CPU):
+ * VCF record text -> per record the packed presence row (numpy.packbits order, MSB = lowest sample, convert.py:85-86;
+ * present = het or hom-alt of a fully called call of ploidy >= 2, convert.py:64-70), AF = largest alt-allele count /
+ * called alleles (convert.py:75-77), the record's het / hom-alt cell counts (convert.py:64-69) and its singleton flag
+ * (counts[1] == 1 or counts[0] == 1, convert.py:58-61).  The caller strips the header (## lines, #CHROM) and inflates.
+ * A context holds two batch slots, each with its own stream, so the host can fill one while the GPU parses the other. */
+#define UTM_VCF_MAX_SAMPLES 524288u          /* the presence row of one record lives in LDS (64 KiB) */
+#define UTM_VCF_MAX_BATCH 4294967232ull      /* 2^32 - 64: offsets inside a batch are 32-bit */
+#define UTM_VCF_SINGLETON 1u                 /* utm_vcf_fetch flags: the record is a singleton (convert.py:58-61) */
+#define UTM_VCF_SKIPPED 2u                   /* ... a `##` line or an empty line among the records: not a variant */
+typedef struct utm_vcf utm_vcf;
+int utm_vcf_create(int device, uint32_t n_samples, uint64_t batch_bytes, utm_vcf **out);
+int utm_vcf_destroy(utm_vcf *vcf);
+/* Pinned staging of the slot the next utm_vcf_parse uses, grown to at least n_bytes (contents kept): the caller may
+ * read or inflate the batch straight into it.  *cap = its size. */
+int utm_vcf_staging(utm_vcf *vcf, uint64_t n_bytes, uint8_t **buf, uint64_t *cap);
+/* Queue one batch: n_bytes of whole records, the last one ending in '\n' (CR before it is dropped).  text may be the
+ * staging buffer (no copy) or any host memory.  Returns once the text is on the device and the parse is queued;
+ * *n_records = lines in the batch (skipped lines included).  At most two batches wait for utm_vcf_fetch. */
+int utm_vcf_parse(utm_vcf *vcf, const uint8_t *text, uint64_t n_bytes, uint64_t *n_records);
+/* Wait for the oldest queued batch and copy its results out: rows[n_records * ceil(S/8)], af, n_het, n_hom and flags
+ * (UTM_VCF_*) per line.  A malformed record (fewer than ten columns, a sample count other than the header's, no GT,
+ * an allele token that is neither `.` nor an unsigned decimal, more than 4096 alt alleles, #CHROM among the records)
+ * fails the batch with UTM_EINVAL naming its line in the batch; the context stays usable. */
+int utm_vcf_fetch(utm_vcf *vcf, uint8_t *rows, double *af, uint32_t *n_het, uint32_t *n_hom, uint8_t *flags);
+/* HIP-event time summed over the fetched batches: ms[0] host-to-device text, ms[1] kernels, ms[2] device-to-host results. */
+int utm_vcf_timing(utm_vcf *vcf, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

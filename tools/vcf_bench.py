@@ -1,0 +1,149 @@
+"""VCF ingest benchmark: the CPU reader (utmos_amd/vcfio.read_vcf) against the GPU reader (utmos_amd/vcfgpu.py) on one
+seeded synthetic call set, uncompressed and BGZF, end to end in the same process, with the GPU reader's phase split.
+
+    python tools/vcf_bench.py --out DIR [--records 200000] [--samples 2504] [--seed 1] [--device 0]
+
+Writes DIR/synth.vcf and DIR/synth.vcf.gz (BGZF, zlib level 1: inflate speed barely depends on the level), prints one
+JSON line and writes it to DIR/vcf_bench.json.  The call set: FORMAT GT, `a|b` / `a/b` diploid calls, about 10 % of
+records multi-allelic (2-3 alt alleles), 1 % missing alleles.  Phases (seconds unless named _ms):
+  fill_s      host: reading (plain) or inflating (BGZF, thread pool) the text into the pinned staging
+  h2d_ms, kernel_ms, d2h_ms   HIP-event time of the copies and of the four parse kernels, summed over the batches
+  total_s     the whole call, header to the assembled arrays
+Kernel time for a text GB/s figure is best taken from a `rocprofv3 --kernel-trace --stats` run of this tool; stream_gbps
+is the streaming-read calibration of this GPU (utm_stream_calibration) to hold it against.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def synth_text(seed, n_rec, n_samp, block=5000):
+    """Yields the VCF text in pieces: header first, then `block` records at a time."""
+    rng = np.random.default_rng(seed)
+    yield ("##fileformat=VCFv4.2\n##source=vcf_bench\n" + "\t".join(
+        ["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + [f"HG{i:05d}" for i in range(n_samp)]) + "\n").encode()
+    for b0 in range(0, n_rec, block):
+        nb = min(block, n_rec - b0)
+        n_alt = np.where(rng.random(nb) < 0.1, rng.integers(2, 4, nb), 1)
+        af = rng.beta(0.3, 3.0, nb)[:, None]
+        cells = np.empty((nb, n_samp, 4), np.uint8)
+        for k in (0, 2):
+            carrier = rng.random((nb, n_samp)) < af
+            allele = np.where(carrier, rng.integers(1, n_alt[:, None] + 1, (nb, n_samp)), 0)
+            ch = (allele + 48).astype(np.uint8)
+            ch[rng.random((nb, n_samp)) < 0.01] = ord(".")
+            cells[:, :, k] = ch
+        cells[:, :, 1] = np.where(rng.random((nb, n_samp)) < 0.9, ord("|"), ord("/"))
+        cells[:, :, 3] = ord("\t")
+        cells[:, -1, 3] = ord("\n")
+        alts = {1: "C", 2: "C,G", 3: "C,G,T"}
+        parts = []
+        for i in range(nb):
+            parts.append(f"chr1\t{1000 + b0 + i}\t.\tA\t{alts[int(n_alt[i])]}\t.\tPASS\t.\tGT\t".encode())
+            parts.append(cells[i].tobytes())
+        yield b"".join(parts)
+
+
+def write_inputs(out, seed, n_rec, n_samp):
+    from utmos_amd.vcfgpu import bgzf_compress
+    plain, bgz = os.path.join(out, "synth.vcf"), os.path.join(out, "synth.vcf.gz")
+    t0 = time.perf_counter()
+    with open(plain, "wb") as fp, open(bgz, "wb") as fz:
+        for piece in synth_text(seed, n_rec, n_samp):
+            fp.write(piece)
+            fz.write(bgzf_compress(piece, level=1)[:-28])   # (one end-of-file member, at the end)
+        fz.write(bgzf_compress(b"", level=1))
+    return plain, bgz, time.perf_counter() - t0
+
+
+def inflate_only(path, threads):
+    """Seconds to inflate the whole BGZF file into a 64 MiB buffer, nothing else."""
+    from utmos_amd.vcfgpu import open_source
+    buf = np.empty(64 << 20, np.uint8)
+    t0 = time.perf_counter()
+    src = open_source(path, threads)
+    n = 0
+    try:
+        while True:
+            k = src.fill(memoryview(buf))
+            if not k:
+                break
+            n += k
+    finally:
+        src.close()
+    return time.perf_counter() - t0, n
+
+
+def same(a, b):
+    return (a["GT"].shape == b["GT"].shape and bool((a["GT"] == b["GT"]).all())
+            and bool((a["AF"].view(np.int64) == b["AF"].view(np.int64)).all())
+            and [str(s) for s in a["samples"]] == [str(s) for s in b["samples"]])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--records", type=int, default=200_000)
+    ap.add_argument("--samples", type=int, default=2504)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--skip-cpu", action="store_true", help="GPU reader only (e.g. under a profiler)")
+    args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    from utmos_amd import device, vcfgpu, vcfio
+
+    plain, bgz, gen_s = write_inputs(args.out, args.seed, args.records, args.samples)
+    text_bytes = os.path.getsize(plain)
+    res = {"records": args.records, "samples": args.samples, "text_bytes": text_bytes, "bgzf_bytes": os.path.getsize(bgz),
+           "generate_s": round(gen_s, 2), "inflate_threads": vcfgpu.inflate_threads()}
+
+    # inflate alone: one thread, then the pool the reader uses
+    for label, threads in (("1", 1), ("pool", vcfgpu.inflate_threads())):
+        s, n = inflate_only(bgz, threads)
+        assert n == text_bytes
+        res[f"inflate_{label}_thread_s" if label == "1" else "inflate_pool_s"] = round(s, 3)
+
+    with vcfgpu.GpuVcfReader(device=args.device) as reader:
+        reader.read(os.path.join(ROOT, "tests", "golden", "vcf", "chunk0.vcf.gz"))    # warm-up: code objects, context
+        gpu = {}
+        for form, path in (("plain", plain), ("bgzf", bgz)):
+            got = reader.read(path)
+            gpu[form] = got
+            res[f"gpu_{form}"] = {k: round(v, 3) for k, v in reader.timing.items()}
+        assert same(gpu["plain"], gpu["bgzf"])
+        kernel_s = res["gpu_plain"]["kernel_ms"] / 1e3
+        res["gpu_kernel_text_gbps_events"] = round(text_bytes / kernel_s / 1e9, 1) if kernel_s else None
+
+    if not args.skip_cpu:
+        for form, path in (("plain", plain), ("bgzf", bgz)):
+            t0 = time.perf_counter()
+            want = vcfio.read_vcf(path)
+            res[f"cpu_{form}_s"] = round(time.perf_counter() - t0, 3)
+            res[f"equal_{form}"] = same(gpu[form], want)
+            res[f"speedup_{form}"] = round(res[f"cpu_{form}_s"] / res[f"gpu_{form}"]["total_s"], 2)
+            del want
+
+    # streaming-read calibration of this GPU (the shape the selection kernels are held against)
+    with device.DeviceMatrix(2504, device=args.device) as m:
+        c = m.add_chunk(2_000_000)
+        m.synth_fill(c, seed=1)
+        res["stream_gbps"] = round(m.stream_calibration(20), 1)
+    if res.get("gpu_kernel_text_gbps_events"):
+        res["kernel_text_frac_of_stream"] = round(res["gpu_kernel_text_gbps_events"] / res["stream_gbps"], 3)
+    line = json.dumps(res)
+    print(line)
+    with open(os.path.join(args.out, "vcf_bench.json"), "w") as fh:
+        fh.write(line + "\n")
+    if not args.skip_cpu and not (res["equal_plain"] and res["equal_bgzf"]):
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()

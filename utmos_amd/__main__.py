@@ -1,9 +1,9 @@
 """Command line front end: ``python -m utmos_amd <command> [options]``.
 
 Commands: ``select`` (the MI355X greedy selection, same flags and output as the reference's
-``utmos select``, utmos/__main__.py:17-47 dispatches it the same way) and ``version``.
-``convert`` belongs to the reference's VCF tooling and is not part of this build; ``select`` reads
-``.vcf[.gz]``, ``.jl`` and ``.npz`` inputs directly.
+``utmos select``, utmos/__main__.py:17-47 dispatches it the same way), ``convert`` (a VCF's genotypes -> the
+reference's .jl part file, parsed on the GPU; utmos/convert.py) and ``version``.  ``select`` reads ``.vcf[.gz]``,
+``.jl`` and ``.npz`` inputs directly.
 """
 import sys
 
@@ -14,6 +14,7 @@ def _usage():
     return (f"Utmos v{__version__} (MI355X build)\n"
             "usage: python -m utmos_amd COMMAND [OPTIONS]\n\n"
             "  select    pick the samples that capture the most variants (GPU)\n"
+            "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser)\n"
             "  version   print the version and exit\n")
 
 
@@ -28,9 +29,10 @@ def _run_version(_options):
     return 0
 
 
-def _run_convert(_options):
-    sys.stderr.write("utmos_amd: `convert` is not provided; give the VCF / .jl / .npz files to `select`\n")
-    return 1
+def _run_convert(options):
+    from .convert import cvt_main
+    cvt_main(options)
+    return 0
 
 
 COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert}

@@ -90,6 +90,12 @@ PROTOTYPES = {
     "utm_comm_init": [_P, _I32, _I32, _P],
     "utm_comm_allreduce_max": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_comm_column_by_allreduce": [_P, _I32],
+    "utm_vcf_create": [ctypes.c_int, _U32, _U64, ctypes.POINTER(_P)],
+    "utm_vcf_destroy": [_P],
+    "utm_vcf_staging": [_P, _U64, ctypes.POINTER(_P), ctypes.POINTER(_U64)],
+    "utm_vcf_parse": [_P, _P, _U64, ctypes.POINTER(_U64)],
+    "utm_vcf_fetch": [_P, _P, _P, _P, _P, _P],
+    "utm_vcf_timing": [_P, ctypes.POINTER(ctypes.c_double)],
 }
 
 _lib = None

@@ -1,0 +1,67 @@
+"""`convert`: a VCF's genotypes -> the reference's lightweight part file (utmos/convert.py), parsed on the GPU.
+
+Output (utmos/convert.py:79-98): joblib.dump({"samples", "GT" (numpy.packbits rows), "AF" (n, 1) float64,
+"stats": {"num_het", "num_hom"}}, compress=L) -- what the reference's `select` loads with joblib.load.  An output
+name ending in .npz holds GT, AF and samples instead (no pickle; `select` reads it as well).
+"""
+import argparse
+import logging
+import sys
+
+import numpy as np
+
+from .select import setup_logging
+
+
+def parse_args(args):
+    """The reference's flags (utmos/convert.py:16-40) plus --device."""
+    parser = argparse.ArgumentParser(prog="convert", description="Convert a VCF's genotypes to a lightweight numpy part file (GPU parser).")
+    parser.add_argument("in_file", type=str, help="Input VCF (.vcf, .vcf.gz; BGZF is inflated in parallel)")
+    parser.add_argument("out_file", type=str, help="Output joblib (.jl), or .npz")
+    parser.add_argument("--no-singleton", action="store_true", help="Remove singleton variants")
+    parser.add_argument("--lowmem", action="store_true",
+                        help="Accepted for compatibility (the reference's hdf5 temporary file); the GPU reader always "
+                             "streams the VCF in batches and holds only the packed rows (%(default)s)")
+    parser.add_argument("-B", "--buffer", type=int, default=50000,
+                        help="Accepted for compatibility (the reference's scikit-allel chunk length); batches here are "
+                             "cut by bytes (%(default)s)")
+    parser.add_argument("-c", "--compress", type=int, default=5, help="joblib compress level 1-9 (%(default)s)")
+    parser.add_argument("--device", type=int, default=0, help="GPU index (%(default)s)")
+    return parser.parse_args(args)
+
+
+def convert(in_file, no_singleton=False, device=0):
+    """-> the part dict of utmos/convert.py:read_vcf (singleton rows dropped before the stats when asked)."""
+    from .vcfgpu import read_vcf
+    part = read_vcf(in_file, device=device)
+    gt, af, het, hom = part["GT"], part["AF"], part["het"], part["hom"]
+    logging.info("%d variants x %d samples", gt.shape[0], len(part["samples"]))
+    if no_singleton:
+        keep = ~part["singleton"]
+        logging.info("Removing %d singletons", int((~keep).sum()))
+        gt, af, het, hom = gt[keep], af[keep], het[keep], hom[keep]
+    stats = {"num_het": np.int64(het.sum(dtype=np.int64)), "num_hom": np.int64(hom.sum(dtype=np.int64))}
+    logging.info("%d hets, %d homs", stats["num_het"], stats["num_hom"])
+    return {"samples": np.asarray(part["samples"]), "GT": gt, "AF": af, "stats": stats}
+
+
+def write(data, out_file, compress=5):
+    if out_file.endswith(".npz"):
+        np.savez(out_file, GT=data["GT"], AF=data["AF"], samples=np.asarray(data["samples"]).astype(str))
+        return
+    import joblib  # the reference's container (utmos/convert.py:98)
+    data = dict(data, samples=np.asarray(data["samples"]).astype(object))
+    joblib.dump(data, out_file, compress=compress)
+
+
+def cvt_main(cmdargs):
+    args = parse_args(cmdargs)
+    setup_logging()
+    try:
+        data = convert(args.in_file, args.no_singleton, args.device)
+    except (OSError, ValueError) as err:
+        logging.error("%s", err)
+        sys.exit(1)
+    logging.info("Saving genotypes")
+    write(data, args.out_file, args.compress)
+    logging.info("Finished conversion")

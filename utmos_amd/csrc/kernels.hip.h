@@ -11,3 +11,4 @@
 #include "loop_int.hip.h"
 #include "af_defer.hip.h"
 #include "ingest.hip.h"
+#include "vcf.hip.h"

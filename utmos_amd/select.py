@@ -152,11 +152,16 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
 
 
 # ---------------------------------------------------------------------------------------------- ingest
-def _read_part(path):
-    """One input file -> {'GT': packbits rows, 'AF': per-variant float64, 'samples'} (the reference's part dict)."""
+def _read_part(path, dev=0):
+    """One input file -> {'GT': packbits rows, 'AF': per-variant float64, 'samples'} (the reference's part dict).
+    VCFs are parsed on the run's GPU (vcfgpu.py)."""
     if path.endswith((".vcf.gz", ".vcf")):
-        from .vcfio import read_vcf
-        return read_vcf(path)
+        from .vcfgpu import read_vcf
+        try:
+            return read_vcf(path, device=dev)
+        except ValueError as err:
+            logging.error("%s", err)
+            sys.exit(1)
     if path.endswith(".jl"):
         import joblib  # the reference's own container (utmos/convert.py:98)
         return joblib.load(path)
@@ -240,7 +245,7 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
 
     samples = matrix = builder = writer = None
     for number, path in enumerate(in_files, start=1):
-        part = _read_part(path)
+        part = _read_part(path, dev)
         if samples is None:
             samples = np.asarray(part["samples"]).astype("U")
             matrix = _shard_matrix(len(samples), dev, shard)
