@@ -316,6 +316,26 @@ int utm_vcf_parse(utm_vcf *vcf, const uint8_t *text, uint64_t n_bytes, uint64_t 
 int utm_vcf_fetch(utm_vcf *vcf, uint8_t *rows, double *af, uint32_t *n_het, uint32_t *n_hom, uint8_t *flags);
 /* HIP-event time summed over the fetched batches: ms[0] host-to-device text, ms[1] kernels, ms[2] device-to-host results. */
 int utm_vcf_timing(utm_vcf *vcf, double *ms);
+/* BGZF batches inflated on the device.  `packed` holds n_members whole BGZF members back to back (it may be the staging
+ * of utm_vcf_staging: no copy); members[2 i] = member i's size in bytes (BSIZE + 1), members[2 i + 1] its ISIZE.  The
+ * text of the batch is: the carry of the previous batch, then prefix[0, prefix_bytes) (the first batch: the text after
+ * the header, inflated by the caller), then the members' text.  Records are cut at the last newline; the bytes after it
+ * (*carry_bytes; the whole batch when it has no newline) stay on the device and open the next batch.  flags:
+ * UTM_BGZF_FIRST starts a file (drops any carry), UTM_BGZF_LAST ends it (a final record without a newline gets one).
+ * Every member is checked (block structure, CRC32, ISIZE); a bad one fails the call with UTM_EINVAL and
+ * utm_last_error() = "member <i> of the batch: <reason>", and the context stays usable.  Otherwise as utm_vcf_parse. */
+#define UTM_BGZF_FIRST 1u
+#define UTM_BGZF_LAST 2u
+int utm_vcf_parse_bgzf(utm_vcf *vcf, const uint8_t *prefix, uint64_t prefix_bytes, const uint8_t *packed,
+                       uint64_t packed_bytes, const uint32_t *members, uint64_t n_members, uint32_t flags,
+                       uint64_t *n_records, uint64_t *carry_bytes);
+/* HIP-event time of the BGZF inflate kernels summed over the fetched batches (ms[0]). */
+int utm_vcf_inflate_timing(utm_vcf *vcf, double *ms);
+/* The device's BGZF member decoder built for the CPU: one whole member (gzip header to trailer) -> its text, at most
+ * out_cap bytes of it copied to out.  *status = 0 when the member is good (structure, CRC32, ISIZE), else a nonzero
+ * code in bits 0-7; bits 8.. hold the bytes decoded.  Needs no GPU. */
+int utm_bgzf_inflate_host(const uint8_t *member, uint64_t member_bytes, uint8_t *out, uint64_t out_cap,
+                          uint32_t *status);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,16 @@
 """VCF ingest benchmark: the CPU reader (utmos_amd/vcfio.read_vcf) against the GPU reader (utmos_amd/vcfgpu.py) on one
 seeded synthetic call set, uncompressed and BGZF, end to end in the same process, with the GPU reader's phase split.
 
-    python tools/vcf_bench.py --out DIR [--records 200000] [--samples 2504] [--seed 1] [--device 0]
+    python tools/vcf_bench.py --out DIR [--records 200000] [--samples 2504] [--seed 1] [--device 0] [--inflate both]
 
 Writes DIR/synth.vcf and DIR/synth.vcf.gz (BGZF, zlib level 1: inflate speed barely depends on the level), prints one
 JSON line and writes it to DIR/vcf_bench.json.  The call set: FORMAT GT, `a|b` / `a/b` diploid calls, about 10 % of
 records multi-allelic (2-3 alt alleles), 1 % missing alleles.  Phases (seconds unless named _ms):
-  fill_s      host: reading (plain) or inflating (BGZF, thread pool) the text into the pinned staging
+  fill_s      host: reading (plain) or inflating (BGZF, thread pool) the text into the pinned staging; with BGZF
+              inflated on the GPU, reading the compressed members into the staging
   h2d_ms, kernel_ms, d2h_ms   HIP-event time of the copies and of the four parse kernels, summed over the batches
+  inflate_ms  HIP-event time of the BGZF inflate kernels (GPU inflation only)
+BGZF is read with GPU inflation (gpu_bgzf) and with host inflation (gpu_bgzf_host_inflate); --inflate picks one.
   total_s     the whole call, header to the assembled arrays
 Kernel time for a text GB/s figure is best taken from a `rocprofv3 --kernel-trace --stats` run of this tool; stream_gbps
 is the streaming-read calibration of this GPU (utm_stream_calibration) to hold it against.
@@ -95,6 +98,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--skip-cpu", action="store_true", help="GPU reader only (e.g. under a profiler)")
+    ap.add_argument("--inflate", choices=["both", "gpu", "host"], default="both",
+                    help="BGZF through the GPU reader with GPU inflation, host inflation, or both [both]")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     from utmos_amd import device, vcfgpu, vcfio
@@ -110,14 +115,24 @@ def main():
         assert n == text_bytes
         res[f"inflate_{label}_thread_s" if label == "1" else "inflate_pool_s"] = round(s, 3)
 
-    with vcfgpu.GpuVcfReader(device=args.device) as reader:
-        reader.read(os.path.join(ROOT, "tests", "golden", "vcf", "chunk0.vcf.gz"))    # warm-up: code objects, context
-        gpu = {}
-        for form, path in (("plain", plain), ("bgzf", bgz)):
-            got = reader.read(path)
-            gpu[form] = got
+    runs = [("plain", plain, "auto")]
+    if args.inflate in ("both", "gpu"):
+        runs.append(("bgzf", bgz, "gpu"))
+    if args.inflate in ("both", "host"):
+        runs.append(("bgzf_host_inflate", bgz, "host"))
+    gpu = {}
+    for form, path, inflate in runs:
+        with vcfgpu.GpuVcfReader(device=args.device, inflate=inflate) as reader:
+            reader.read(os.path.join(ROOT, "tests", "golden", "vcf", "chunk0.vcf.gz"))  # warm-up: code objects, context
+            gpu[form] = reader.read(path)
             res[f"gpu_{form}"] = {k: round(v, 3) for k, v in reader.timing.items()}
-        assert same(gpu["plain"], gpu["bgzf"])
+        assert same(gpu["plain"], gpu[form])
+    if "bgzf" not in gpu:
+        gpu["bgzf"] = gpu["bgzf_host_inflate"]
+    if "gpu_bgzf" in res:
+        res["gpu_bgzf_inflate_text_gbps_events"] = round(text_bytes / res["gpu_bgzf"]["inflate_ms"] / 1e6, 1)
+    if "gpu_bgzf" in res and "gpu_bgzf_host_inflate" in res:
+        res["speedup_bgzf_gpu_over_host_inflate"] = round(res["gpu_bgzf_host_inflate"]["total_s"] / res["gpu_bgzf"]["total_s"], 2)
         kernel_s = res["gpu_plain"]["kernel_ms"] / 1e3
         res["gpu_kernel_text_gbps_events"] = round(text_bytes / kernel_s / 1e9, 1) if kernel_s else None
 
@@ -127,7 +142,7 @@ def main():
             want = vcfio.read_vcf(path)
             res[f"cpu_{form}_s"] = round(time.perf_counter() - t0, 3)
             res[f"equal_{form}"] = same(gpu[form], want)
-            res[f"speedup_{form}"] = round(res[f"cpu_{form}_s"] / res[f"gpu_{form}"]["total_s"], 2)
+            res[f"speedup_{form}"] = round(res[f"cpu_{form}_s"] / res["gpu_" + (form if f"gpu_{form}" in res else "bgzf_host_inflate")]["total_s"], 2)
             del want
 
     # streaming-read calibration of this GPU (the shape the selection kernels are held against)

@@ -14,7 +14,7 @@ def _usage():
     return (f"Utmos v{__version__} (MI355X build)\n"
             "usage: python -m utmos_amd COMMAND [OPTIONS]\n\n"
             "  select    pick the samples that capture the most variants (GPU)\n"
-            "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser)\n"
+            "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser; BGZF inflated on the GPU)\n"
             "  version   print the version and exit\n")
 
 

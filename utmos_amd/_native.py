@@ -96,6 +96,9 @@ PROTOTYPES = {
     "utm_vcf_parse": [_P, _P, _U64, ctypes.POINTER(_U64)],
     "utm_vcf_fetch": [_P, _P, _P, _P, _P, _P],
     "utm_vcf_timing": [_P, ctypes.POINTER(ctypes.c_double)],
+    "utm_vcf_parse_bgzf": [_P, _P, _U64, _P, _U64, _P, _U64, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
+    "utm_vcf_inflate_timing": [_P, ctypes.POINTER(ctypes.c_double)],
+    "utm_bgzf_inflate_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U32)],
 }
 
 _lib = None

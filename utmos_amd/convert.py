@@ -16,7 +16,8 @@ from .select import setup_logging
 def parse_args(args):
     """The reference's flags (utmos/convert.py:16-40) plus --device."""
     parser = argparse.ArgumentParser(prog="convert", description="Convert a VCF's genotypes to a lightweight numpy part file (GPU parser).")
-    parser.add_argument("in_file", type=str, help="Input VCF (.vcf, .vcf.gz; BGZF is inflated in parallel)")
+    parser.add_argument("in_file", type=str,
+                        help="Input VCF (.vcf, .vcf.gz; BGZF is inflated on the GPU unless --inflate host)")
     parser.add_argument("out_file", type=str, help="Output joblib (.jl), or .npz")
     parser.add_argument("--no-singleton", action="store_true", help="Remove singleton variants")
     parser.add_argument("--lowmem", action="store_true",
@@ -27,13 +28,16 @@ def parse_args(args):
                              "cut by bytes (%(default)s)")
     parser.add_argument("-c", "--compress", type=int, default=5, help="joblib compress level 1-9 (%(default)s)")
     parser.add_argument("--device", type=int, default=0, help="GPU index (%(default)s)")
+    parser.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
+                        help="where BGZF members are inflated: auto / gpu on the device (gpu refuses gzip that is not "
+                             "BGZF), host on a thread pool (%(default)s)")
     return parser.parse_args(args)
 
 
-def convert(in_file, no_singleton=False, device=0):
+def convert(in_file, no_singleton=False, device=0, inflate="auto"):
     """-> the part dict of utmos/convert.py:read_vcf (singleton rows dropped before the stats when asked)."""
     from .vcfgpu import read_vcf
-    part = read_vcf(in_file, device=device)
+    part = read_vcf(in_file, device=device, inflate=inflate)
     gt, af, het, hom = part["GT"], part["AF"], part["het"], part["hom"]
     logging.info("%d variants x %d samples", gt.shape[0], len(part["samples"]))
     if no_singleton:
@@ -58,7 +62,7 @@ def cvt_main(cmdargs):
     args = parse_args(cmdargs)
     setup_logging()
     try:
-        data = convert(args.in_file, args.no_singleton, args.device)
+        data = convert(args.in_file, args.no_singleton, args.device, args.inflate)
     except (OSError, ValueError) as err:
         logging.error("%s", err)
         sys.exit(1)

@@ -12,3 +12,4 @@
 #include "af_defer.hip.h"
 #include "ingest.hip.h"
 #include "vcf.hip.h"
+#include "inflate.hip.h"

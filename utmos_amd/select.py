@@ -152,13 +152,13 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
 
 
 # ---------------------------------------------------------------------------------------------- ingest
-def _read_part(path, dev=0):
+def _read_part(path, dev=0, inflate="auto"):
     """One input file -> {'GT': packbits rows, 'AF': per-variant float64, 'samples'} (the reference's part dict).
-    VCFs are parsed on the run's GPU (vcfgpu.py)."""
+    VCFs are parsed on the run's GPU (vcfgpu.py); `inflate` says where BGZF is inflated."""
     if path.endswith((".vcf.gz", ".vcf")):
         from .vcfgpu import read_vcf
         try:
-            return read_vcf(path, device=dev)
+            return read_vcf(path, device=dev, inflate=inflate)
         except ValueError as err:
             logging.error("%s", err)
             sys.exit(1)
@@ -228,7 +228,7 @@ class _ChunkBuilder:
         self.chunk_af.append(af)
 
 
-def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None):
+def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto"):
     """Load and concatenate the inputs into one HBM-resident matrix -> {"samples", "data", "var_count", "has_af"}.
 
     lowmem == 1: in_files[0] is an existing packed store.  lowmem == path: the store is (re)created there while
@@ -245,7 +245,7 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
 
     samples = matrix = builder = writer = None
     for number, path in enumerate(in_files, start=1):
-        part = _read_part(path, dev)
+        part = _read_part(path, dev, inflate)
         if samples is None:
             samples = np.asarray(part["samples"]).astype("U")
             matrix = _shard_matrix(len(samples), dev, shard)
@@ -355,6 +355,9 @@ def _build_parser():
                           "subtract what the last winner newly captured; identical output)")
     gpu.add_argument("--exchange", choices=["auto", "mailboxes", "rccl", "rccl-allreduce"], default="auto",
                      help="several processes: how the shards meet every iteration [auto: device mailboxes, else RCCL]")
+    gpu.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
+                     help="where BGZF (.vcf.gz from bgzip) input is inflated: on the GPU (auto, gpu) or by host "
+                          "threads (host); gpu refuses gzip that is not BGZF [%(default)s]")
     return parser
 
 
@@ -409,7 +412,8 @@ def select_main(cmdargs):
         dev = args.device
     else:   # one GPU per rank on a full node (ranks share devices only on smaller test boxes)
         dev = local_rank % device.nat.device_count() if world > 1 else 0
-    data = load_files(args.in_files, args.lowmem, args.buffer, args.af, dev, (rank, world) if world > 1 else None)
+    data = load_files(args.in_files, args.lowmem, args.buffer, args.af, dev, (rank, world) if world > 1 else None,
+                      args.inflate)
     matrix = data["data"]
     if not args.brute_force:
         matrix.set_decremental(True)            # exact; same rows (DESIGN.md "Decremental scoring")

@@ -1,9 +1,13 @@
 """VCF genotype reader on the GPU: the same dict as vcfio.read_vcf, parsed by the HIP kernels of csrc/vcf.hip.h.
 
 The host reads the header (``##`` lines, the sample names of ``#CHROM``), then streams the records in batches cut at
-the last newline: plain text straight into the parse context's pinned staging, BGZF members (the block gzip of
-bgzip / htslib: a gzip member with a ``BC`` extra field holding its size) inflated by a thread pool, any other gzip as
-one stream.  While the GPU parses one batch the host fills the other slot.  The kernels return per record the packed
+the last newline: plain text straight into the parse context's pinned staging, any gzip that is not BGZF as one
+stream.  BGZF (the block gzip of bgzip / htslib: gzip members with a ``BC`` extra field holding their size) is inflated
+on the GPU by default (``inflate="auto"`` or ``"gpu"``, csrc/inflate.hip.h): the host inflates only the members that
+hold the header, then reads compressed members straight into the staging, cut into batches at member borders, and the
+device inflates, checks and parses them; a record that crosses a batch border stays on the device.  ``inflate="host"``
+inflates BGZF members on a thread pool instead and cuts batches at newlines on the host.  While the GPU parses one
+batch the host fills the other slot.  The kernels return per record the packed
 presence row, AF, het / hom-alt counts and the singleton flag of the reference's convert (utmos/convert.py:43-88).
 
 Contract: for every input on which vcfio.read_vcf succeeds and whose allele tokens are all ``.`` or unsigned decimals
@@ -25,6 +29,8 @@ import numpy as np
 from . import _native as nat
 
 DEFAULT_BATCH_BYTES = 64 << 20
+INFLATE_MODES = ("auto", "gpu", "host")
+BGZF_FIRST, BGZF_LAST = 1, 2          # utm_vcf_parse_bgzf flags (UTM_BGZF_FIRST, UTM_BGZF_LAST)
 FLAG_SINGLETON, FLAG_SKIPPED = 1, 2   # utm_vcf_fetch flags (UTM_VCF_SINGLETON, UTM_VCF_SKIPPED)
 UTM_EINVAL = -1
 
@@ -60,6 +66,35 @@ def bgzf_members(buf):
         out.append((off, size, int.from_bytes(buf[off + size - 4:off + size], "little")))
         off += size
     return out
+
+
+class _MemberSource:
+    """BGZF members inflated on the host one per fill (the header's members on the GPU path)."""
+
+    def __init__(self, path, mm, members):
+        self.path, self.mm, self.members = path, mm, members
+        self.next = 0
+        self.rest = b""
+
+    def fill(self, view):
+        if not self.rest:
+            if self.next == len(self.members):
+                return 0
+            off, size, isize = self.members[self.next]
+            try:
+                self.rest = zlib.decompress(memoryview(self.mm)[off:off + size], 31)
+            except zlib.error as err:
+                raise ValueError(f"{self.path}: BGZF member at byte {off}: {err}") from None
+            if len(self.rest) != isize:
+                raise ValueError(f"{self.path}: BGZF member at byte {off}: {len(self.rest)} bytes inflated, ISIZE says {isize}")
+            self.next += 1
+        k = min(len(view), len(self.rest))
+        view[:k] = self.rest[:k]
+        self.rest = self.rest[k:]
+        return k
+
+    def close(self):
+        pass
 
 
 class _StreamSource:
@@ -165,8 +200,12 @@ def _last_newline(arr, n):
 class GpuVcfReader:
     """A parse context on one GPU, reusable across files (it is rebuilt only when the sample count changes)."""
 
-    def __init__(self, device=0, batch_bytes=DEFAULT_BATCH_BYTES, threads=None):
-        self.device, self.batch_bytes, self.threads = int(device), int(batch_bytes), threads
+    def __init__(self, device=0, batch_bytes=DEFAULT_BATCH_BYTES, threads=None, inflate="auto"):
+        """inflate: where BGZF members are inflated -- "auto" / "gpu" on the device, "host" on a thread pool.  "gpu"
+        on a gzip file that is not BGZF raises ValueError; plain text and single-stream gzip read the same either way."""
+        if inflate not in INFLATE_MODES:
+            raise ValueError(f"inflate={inflate!r}: one of {', '.join(INFLATE_MODES)}")
+        self.device, self.batch_bytes, self.threads, self.inflate = int(device), int(batch_bytes), threads, inflate
         self.handle, self.n_samples = None, None
         self.timing = {}
 
@@ -220,9 +259,17 @@ class GpuVcfReader:
 
     def read(self, path):
         """-> {'GT', 'AF' (n, 1), 'samples', 'stats': {'num_het', 'num_hom'}, 'singleton' (n,) bool}; self.timing holds
-        the phase split of this call (seconds: fill = read / inflate on the host; ms: h2d, kernels, d2h)."""
+        the phase split of this call (seconds: fill = read / inflate on the host -- with BGZF inflated on the GPU, reading
+        the compressed bytes; ms: h2d, kernels, d2h, inflate = the GPU inflate kernels)."""
         lib = nat.lib()
         t0 = time.perf_counter()
+        if path.endswith(".gz") and self.inflate != "host":
+            with open(path, "rb") as fh:
+                bgzf = is_bgzf(fh.read(18))
+            if bgzf:
+                return self._read_bgzf(path, t0)
+            if self.inflate == "gpu":
+                raise ValueError(f"{path}: inflate='gpu' needs BGZF (bgzip) input; this gzip file is one stream")
         src = open_source(path, self.threads)
         fill_s = 0.0
         try:
@@ -284,7 +331,91 @@ class GpuVcfReader:
         finally:
             src.close()
         self.timing = {"fill_s": fill_s, "h2d_ms": ms1[0] - ms0[0], "kernel_ms": ms1[1] - ms0[1],
-                       "d2h_ms": ms1[2] - ms0[2], "total_s": time.perf_counter() - t0}
+                       "d2h_ms": ms1[2] - ms0[2], "inflate_ms": 0.0, "total_s": time.perf_counter() - t0}
+        return self._assemble(parts, samples, width)
+
+    def _read_bgzf(self, path, t0):
+        """BGZF inflated on the GPU: members after the header's go to the device compressed, in batches of whole
+        members (ISIZE summed up to batch_bytes); the device keeps a record that crosses a batch border."""
+        lib = nat.lib()
+        with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            try:
+                members = bgzf_members(mm)
+            except ValueError as err:
+                raise ValueError(f"{path}: {err}") from None
+            hs = _MemberSource(path, mm, members)
+            samples, n_head, prefix = self._header(path, hs)
+            prefix += hs.rest
+            if len(samples) == 0:
+                return self._no_samples(path, hs, samples, prefix)
+            h = self._context(len(samples))
+            ms0, inf0 = (ctypes.c_double * 3)(), ctypes.c_double()
+            nat.check(lib.utm_vcf_timing(h, ms0))
+            nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf0)))
+            width = (len(samples) + 7) // 8
+            table = np.array(members, dtype=np.int64).reshape(-1, 3)
+            off, size, isize = table[:, 0], table[:, 1], table[:, 2]
+            ends = np.cumsum(isize)
+            pending, parts, line_base, j, fill_s = deque(), [], 0, hs.next, 0.0
+            flags, failure = BGZF_FIRST, None
+            pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
+            try:
+                while True:
+                    if len(pending) == 2:
+                        parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
+                    k = j
+                    if j < len(members):   # whole members, their text summed up to batch_bytes (at least one)
+                        base = ends[j - 1] if j else 0
+                        k = max(j + 1, int(np.searchsorted(ends, base + self.batch_bytes, side="right")))
+                    last = k == len(members)
+                    packed = int(off[k - 1] + size[k - 1] - off[j]) if k > j else 0
+                    tf = time.perf_counter()
+                    ptr, cap = ctypes.c_void_p(), ctypes.c_uint64()
+                    nat.check(lib.utm_vcf_staging(h, max(packed, 1), ctypes.byref(ptr), ctypes.byref(cap)))
+                    if packed:
+                        view = memoryview((ctypes.c_uint8 * packed).from_address(ptr.value)).cast("B")
+                        fh.seek(int(off[j]))
+                        got = 0
+                        while got < packed:
+                            n = fh.readinto(view[got:])
+                            if not n:
+                                raise ValueError(f"{path}: truncated")
+                            got += n
+                    mem = np.ascontiguousarray(np.stack([size[j:k], isize[j:k]], axis=1), dtype=np.uint32)
+                    fill_s += time.perf_counter() - tf
+                    n_rec, carry = ctypes.c_uint64(), ctypes.c_uint64()
+                    rc = lib.utm_vcf_parse_bgzf(h, pre.ctypes.data if pre is not None else None,
+                                                len(pre) if pre is not None else 0, ptr, packed, mem.ctypes.data,
+                                                k - j, flags | (BGZF_LAST if last else 0), ctypes.byref(n_rec),
+                                                ctypes.byref(carry))
+                    if rc == UTM_EINVAL:
+                        msg = lib.utm_last_error().decode("utf-8", "replace")
+                        m = re.match(r"member (\d+) of the batch: (.*)", msg)
+                        if m:
+                            msg = f"BGZF member at byte {int(off[j + int(m.group(1))])}: {m.group(2)}"
+                        raise ValueError(f"{path}: {msg}")
+                    nat.check(rc)
+                    pending.append((n_rec.value, line_base))
+                    line_base += n_rec.value
+                    flags, pre, j = 0, None, k
+                    if last:
+                        break
+                while pending:
+                    parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
+            except Exception as err:
+                failure = err
+            finally:
+                while pending:                 # drain the other slot: the context stays usable after a failure
+                    pending.popleft()
+                    lib.utm_vcf_fetch(h, None, None, None, None, None)
+            if failure is not None:
+                raise failure
+            ms1, inf1 = (ctypes.c_double * 3)(), ctypes.c_double()
+            nat.check(lib.utm_vcf_timing(h, ms1))
+            nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf1)))
+        self.timing = {"fill_s": fill_s, "h2d_ms": ms1[0] - ms0[0], "kernel_ms": ms1[1] - ms0[1],
+                       "d2h_ms": ms1[2] - ms0[2], "inflate_ms": inf1.value - inf0.value,
+                       "total_s": time.perf_counter() - t0}
         return self._assemble(parts, samples, width)
 
     def _fetch(self, path, h, width, n_head, n_rec, line_base):
@@ -332,9 +463,9 @@ class GpuVcfReader:
         return self._assemble([], samples, 0)
 
 
-def read_vcf(path, device=0, batch_bytes=DEFAULT_BATCH_BYTES, threads=None):
+def read_vcf(path, device=0, batch_bytes=DEFAULT_BATCH_BYTES, threads=None, inflate="auto"):
     """One file through a fresh GpuVcfReader: vcfio.read_vcf's dict plus 'stats' and 'singleton'."""
-    with GpuVcfReader(device, batch_bytes, threads) as reader:
+    with GpuVcfReader(device, batch_bytes, threads, inflate) as reader:
         return reader.read(path)
 
 
