@@ -337,6 +337,43 @@ int utm_vcf_inflate_timing(utm_vcf *vcf, double *ms);
 int utm_bgzf_inflate_host(const uint8_t *member, uint64_t member_bytes, uint8_t *out, uint64_t out_cap,
                           uint32_t *status);
 
+/* ---- DEFLATE encoding (no utm_ctx) ------------------------------------------------------------- */
+/* A raw DEFLATE stream (RFC 1951) compressed on the GPU, for the zlib stream of a joblib part file: the input is cut
+ * into 64 KiB segments at stream offsets, each compressed on its own (fresh 32 KiB window, one dynamic-Huffman block,
+ * or stored blocks when they are smaller).  Every segment but the last ends byte-aligned with an empty stored block
+ * (zlib's Z_SYNC_FLUSH); the last sets BFINAL.  Levels 1..9 set the match search effort (csrc/deflate.hip.h).  The
+ * caller writes the zlib header and the Adler-32 trailer (utm_deflate_adler).  The bytes depend only on the input, the
+ * level and the segment borders: utm_deflate_host produces the same bytes on the CPU. */
+#define UTM_DEFLATE_MAX_BATCH 1073741824ull  /* 2^30 input bytes per batch */
+#define UTM_DEFLATE_LAST 1u                  /* utm_deflate_push: the batch ends the stream */
+typedef struct utm_deflate utm_deflate;
+/* *bound = the most raw-deflate bytes n_bytes of input can take: n + 15 per started 64 KiB segment (at least one). */
+int utm_deflate_bound(uint64_t n_bytes, uint64_t *bound);
+/* A context for batches of up to batch_bytes (rounded up to a multiple of 64 KiB) at one level. */
+int utm_deflate_create(int device, uint64_t batch_bytes, int level, utm_deflate **out);
+int utm_deflate_destroy(utm_deflate *deflate);
+/* The pinned staging buffer (*cap = the batch size): a caller may fill it and pass it to utm_deflate_push (no copy). */
+int utm_deflate_staging(utm_deflate *deflate, uint8_t **buf, uint64_t *cap);
+/* Queue one batch of the stream: in[0, n_bytes) (the staging or any host memory).  A batch without UTM_DEFLATE_LAST
+ * must be a multiple of 64 KiB; the last one may be any size up to the batch, 0 included.  Returns once the input is on
+ * the device and the kernels are queued (the staging may be filled again).  At most two batches wait for
+ * utm_deflate_pull.  After a UTM_DEFLATE_LAST batch the next push starts a new stream.  A bad argument changes
+ * nothing. */
+int utm_deflate_push(utm_deflate *deflate, const uint8_t *in, uint64_t n_bytes, uint32_t flags);
+/* Wait for the oldest pushed batch: *out = its compressed bytes in pinned memory, valid until the push after next;
+ * *out_bytes = their count (at most utm_deflate_bound of the batch). */
+int utm_deflate_pull(utm_deflate *deflate, const uint8_t **out, uint64_t *out_bytes);
+/* *adler = the Adler-32 of the current stream's pulled batches (after its last batch: the zlib trailer, big-endian). */
+int utm_deflate_adler(utm_deflate *deflate, uint32_t *adler);
+/* HIP-event time summed over the pulled batches: ms[0] host-to-device input, ms[1] kernels, ms[2] device-to-host output,
+ * ms[3] the part of ms[1] spent in the serial parse (k_deflate_parse). */
+int utm_deflate_timing(utm_deflate *deflate, double *ms);
+/* The device encoder built for the CPU: in[0, n_bytes) as one whole stream at `level` -> out (the same bytes the device
+ * produces), *out_bytes and the stream's Adler-32.  An out_cap below the output fails with UTM_EINVAL and writes
+ * nothing past out_cap.  Needs no GPU. */
+int utm_deflate_host(const uint8_t *in, uint64_t n_bytes, int level, uint8_t *out, uint64_t out_cap,
+                     uint64_t *out_bytes, uint32_t *adler);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,12 @@ records multi-allelic (2-3 alt alleles), 1 % missing alleles.  Phases (seconds u
   inflate_ms  HIP-event time of the BGZF inflate kernels (GPU inflation only)
 BGZF is read with GPU inflation (gpu_bgzf) and with host inflation (gpu_bgzf_host_inflate); --inflate picks one.
   total_s     the whole call, header to the assembled arrays
+The write phase (skip with --skip-write) writes the call set's `convert` part file (.jl, the GT/AF/samples/stats dict)
+from the GPU reader's result: joblib.dump(compress=5) (convert's host path), the same pickle deflated in independent
+64 KiB segments by `min(16, cpus)` host threads (zlib.compressobj per segment, level 5), and GpuZlibWriter at levels
+1 / 5 / 9 (seconds, file bytes, and the writer's HIP-event split: h2d, kernels, parse (part of kernels), d2h).  Every
+file is read back and checked.  `convert` end to end (BGZF input, .jl output at -c 5) is timed with --deflate host and
+--deflate gpu.  --write-only skips the reader comparisons.
 Kernel time for a text GB/s figure is best taken from a `rocprofv3 --kernel-trace --stats` run of this tool; stream_gbps
 is the streaming-read calibration of this GPU (utm_stream_calibration) to hold it against.
 """
@@ -84,6 +90,80 @@ def inflate_only(path, threads):
     return time.perf_counter() - t0, n
 
 
+def segments_host(raw, level, threads):
+    """raw -> a zlib stream of independent 64 KiB segments deflated by a thread pool (zlib releases the GIL)."""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    seg = 1 << 16
+    offs = list(range(0, len(raw), seg)) or [0]
+    view = memoryview(raw)
+
+    def one(off):
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        body = c.compress(view[off:off + seg])
+        return body + (c.flush() if off == offs[-1] else c.flush(zlib.Z_SYNC_FLUSH))
+    with ThreadPoolExecutor(threads) as pool:
+        parts = list(pool.map(one, offs))
+    from utmos_amd.zwrite import zlib_header
+    return zlib_header(level) + b"".join(parts) + zlib.adler32(raw).to_bytes(4, "big")
+
+
+def write_phase(args, bgz, res):
+    """The .jl write: host joblib level 5, host threads on independent segments, the GPU writer at 1 / 5 / 9."""
+    import io
+    import joblib
+    from utmos_amd import convert
+    from utmos_amd.vcfgpu import inflate_threads
+    from utmos_amd.zwrite import GpuZlibWriter
+    data = convert.convert(bgz, device=args.device)
+    data = dict(data, samples=np.asarray(data["samples"]).astype(object))
+    out = {}
+
+    def check(path):
+        got = joblib.load(path)
+        assert (got["GT"] == data["GT"]).all() and (got["AF"] == data["AF"]).all() and got["stats"] == data["stats"]
+
+    path = os.path.join(args.out, "host5.jl")
+    t0 = time.perf_counter()
+    joblib.dump(data, path, compress=5)
+    out["host_joblib_5"] = {"s": round(time.perf_counter() - t0, 3), "bytes": os.path.getsize(path)}
+    check(path)
+    t0 = time.perf_counter()
+    buf = io.BytesIO()
+    joblib.dump(data, buf, compress=0)
+    raw = buf.getvalue()
+    out["pickle_bytes"] = len(raw)
+    out["pickle_s"] = round(time.perf_counter() - t0, 3)
+    threads = inflate_threads()
+    path = os.path.join(args.out, "threads5.jl")
+    t0 = time.perf_counter()
+    with open(path, "wb") as fh:
+        fh.write(segments_host(raw, 5, threads))
+    out[f"host_{threads}_threads_segments_5"] = {"s": round(time.perf_counter() - t0, 3) + out["pickle_s"],
+                                                "bytes": os.path.getsize(path)}
+    check(path)
+    del raw, buf
+    with GpuZlibWriter(io.BytesIO(), 5, args.device) as w:  # warm-up: code objects, pinned buffers
+        w.write(b"warm-up" * 100_000)
+    for level in (1, 5, 9):
+        path = os.path.join(args.out, f"gpu{level}.jl")
+        t0 = time.perf_counter()
+        with GpuZlibWriter(path, level, args.device) as w:
+            joblib.dump(data, w, compress=0)
+        s = time.perf_counter() - t0
+        out[f"gpu_{level}"] = {"s": round(s, 3), "bytes": os.path.getsize(path),
+                               **{k + "_ms": round(v, 2) for k, v in w.final_timing.items()}}
+        check(path)
+    for mode in ("host", "gpu"):
+        path = os.path.join(args.out, f"convert_{mode}.jl")
+        t0 = time.perf_counter()
+        part = convert.convert(bgz, device=args.device)
+        convert.write(part, path, 5, deflate=mode, device=args.device)
+        out[f"convert_bgzf_to_jl_{mode}_s"] = round(time.perf_counter() - t0, 3)
+        check(path)
+    res["write"] = out
+
+
 def same(a, b):
     return (a["GT"].shape == b["GT"].shape and bool((a["GT"] == b["GT"]).all())
             and bool((a["AF"].view(np.int64) == b["AF"].view(np.int64)).all())
@@ -98,6 +178,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--skip-cpu", action="store_true", help="GPU reader only (e.g. under a profiler)")
+    ap.add_argument("--skip-write", action="store_true", help="no write phase")
+    ap.add_argument("--write-only", action="store_true", help="the write phase alone (after one GPU read)")
     ap.add_argument("--inflate", choices=["both", "gpu", "host"], default="both",
                     help="BGZF through the GPU reader with GPU inflation, host inflation, or both [both]")
     args = ap.parse_args()
@@ -109,6 +191,13 @@ def main():
     res = {"records": args.records, "samples": args.samples, "text_bytes": text_bytes, "bgzf_bytes": os.path.getsize(bgz),
            "generate_s": round(gen_s, 2), "inflate_threads": vcfgpu.inflate_threads()}
 
+    if args.write_only:
+        write_phase(args, bgz, res)
+        line = json.dumps(res)
+        print(line)
+        with open(os.path.join(args.out, "vcf_bench.json"), "w") as fh:
+            fh.write(line + "\n")
+        return
     # inflate alone: one thread, then the pool the reader uses
     for label, threads in (("1", 1), ("pool", vcfgpu.inflate_threads())):
         s, n = inflate_only(bgz, threads)
@@ -144,6 +233,9 @@ def main():
             res[f"equal_{form}"] = same(gpu[form], want)
             res[f"speedup_{form}"] = round(res[f"cpu_{form}_s"] / res["gpu_" + (form if f"gpu_{form}" in res else "bgzf_host_inflate")]["total_s"], 2)
             del want
+
+    if not args.skip_write:
+        write_phase(args, bgz, res)
 
     # streaming-read calibration of this GPU (the shape the selection kernels are held against)
     with device.DeviceMatrix(2504, device=args.device) as m:

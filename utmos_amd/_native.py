@@ -99,6 +99,15 @@ PROTOTYPES = {
     "utm_vcf_parse_bgzf": [_P, _P, _U64, _P, _U64, _P, _U64, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
     "utm_vcf_inflate_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_bgzf_inflate_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U32)],
+    "utm_deflate_bound": [_U64, ctypes.POINTER(_U64)],
+    "utm_deflate_create": [ctypes.c_int, _U64, ctypes.c_int, ctypes.POINTER(_P)],
+    "utm_deflate_destroy": [_P],
+    "utm_deflate_staging": [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64)],
+    "utm_deflate_push": [_P, _P, _U64, _U32],
+    "utm_deflate_pull": [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64)],
+    "utm_deflate_adler": [_P, ctypes.POINTER(_U32)],
+    "utm_deflate_timing": [_P, ctypes.POINTER(ctypes.c_double)],
+    "utm_deflate_host": [_P, _U64, ctypes.c_int, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U32)],
 }
 
 _lib = None

@@ -26,11 +26,16 @@ def parse_args(args):
     parser.add_argument("-B", "--buffer", type=int, default=50000,
                         help="Accepted for compatibility (the reference's scikit-allel chunk length); batches here are "
                              "cut by bytes (%(default)s)")
-    parser.add_argument("-c", "--compress", type=int, default=5, help="joblib compress level 1-9 (%(default)s)")
+    parser.add_argument("-c", "--compress", type=int, default=5,
+                        help="joblib compress level 1-9, 0 = uncompressed (%(default)s)")
     parser.add_argument("--device", type=int, default=0, help="GPU index (%(default)s)")
     parser.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
                         help="where BGZF members are inflated: auto / gpu on the device (gpu refuses gzip that is not "
                              "BGZF), host on a thread pool (%(default)s)")
+    parser.add_argument("--deflate", choices=["host", "gpu"], default="host",
+                        help="where a .jl output with -c 1-9 is compressed: host = joblib's zlib, gpu = the DEFLATE "
+                             "encoder on the device (a zlib stream of independent 64 KiB segments; joblib.load reads "
+                             "either) (%(default)s)")
     return parser.parse_args(args)
 
 
@@ -49,12 +54,21 @@ def convert(in_file, no_singleton=False, device=0, inflate="auto"):
     return {"samples": np.asarray(part["samples"]), "GT": gt, "AF": af, "stats": stats}
 
 
-def write(data, out_file, compress=5):
+def write(data, out_file, compress=5, deflate="host", device=0):
+    """deflate="gpu": a .jl output with compress 1-9 is one zlib stream from the GPU encoder (utmos_amd.zwrite)
+    around joblib's uncompressed pickle; everything else is written as before."""
+    if deflate not in ("host", "gpu"):
+        raise ValueError(f"deflate={deflate!r}: expected 'host' or 'gpu'")
     if out_file.endswith(".npz"):
         np.savez(out_file, GT=data["GT"], AF=data["AF"], samples=np.asarray(data["samples"]).astype(str))
         return
     import joblib  # the reference's container (utmos/convert.py:98)
     data = dict(data, samples=np.asarray(data["samples"]).astype(object))
+    if deflate == "gpu" and compress:
+        from .zwrite import GpuZlibWriter
+        with GpuZlibWriter(out_file, compress, device) as w:
+            joblib.dump(data, w, compress=0)
+        return
     joblib.dump(data, out_file, compress=compress)
 
 
@@ -67,5 +81,5 @@ def cvt_main(cmdargs):
         logging.error("%s", err)
         sys.exit(1)
     logging.info("Saving genotypes")
-    write(data, args.out_file, args.compress)
+    write(data, args.out_file, args.compress, args.deflate, args.device)
     logging.info("Finished conversion")

@@ -13,3 +13,4 @@
 #include "ingest.hip.h"
 #include "vcf.hip.h"
 #include "inflate.hip.h"
+#include "deflate.hip.h"

@@ -541,3 +541,4 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_loop.hip.h"
 #include "host_shard.hip.h"
 #include "host_vcf.hip.h"
+#include "host_deflate.hip.h"
