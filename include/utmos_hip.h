@@ -26,47 +26,56 @@
  *     fails with UTM_ESTATE on a shard that has neither.
  *
  * Environment.  None of these changes a result; they move launch shapes and thresholds (tools/tune.py sweeps them)
- * or are test hooks.  ONE table in utmos_amd/csrc/utmos_hip.hip (g_knobs) names them all with their defaults; a context
+ * or are test hooks.  ONE table in utmos_amd/csrc/utmos_hip.hip (g_knobs) names them all with defaults and ranges; a context
  * reads them at utm_ctx_create and again at every utm_reset (read_tune) and nowhere else, so nothing on the
  * per-iteration path touches the environment.  The first context of a process lists on stderr the ones that are set;
  * utm_env_overrides() returns the same list (bench.py reports it as `env_overrides`).
- *   UTM_TARGET_WGS (32768)    workgroups a scoring launch aims for          UTM_MIN_WGS (128), UTM_MIN_WGS_BIG (8192)
- *   UTM_TILE_STEPS (auto)     force the covered tile to 32/16/8/4/2 KiB     smallest grids the 8 KiB / 32 KiB tiles are used for
- *   UTM_NT_LOADS (auto)       non-temporal column loads on/off              UTM_NT_MIN_MB (512) matrix size from which they are used
- *   UTM_FUSE_PICK (1)         pick inside the scoring launch (one shard or mailbox exchange, integer scores)
- *   UTM_CHAIN_PICK (1)        AF with candidate chains: pick inside the chain launch (one shard)
- *   UTM_AF_VERIFY (1)         ... and candidates, compaction, chains and pick as stages of ONE launch (one shard)
- *   UTM_AF_RECORD (1)         AF: a chain's float64 sum stays on record per sample for as long as the sample's count does not change
- *   UTM_AF_DEFER (1)          AF, one shard: exact float64 scores of unambiguous winners are finished per batch from a
+ *   Every knob has a legal range, written here as (default; range): lo..hi, "step" for a multiple, or {the values}.  A
+ *   value outside it, or one that is not a number, is ignored -- the default holds -- and the first context of a process
+ *   names it on stderr.
+ *   UTM_TARGET_WGS (32768; 1..2^24)          workgroups a scoring launch aims for
+ *   UTM_MIN_WGS (128; 0..2^24), UTM_MIN_WGS_BIG (8192; 0..2^24)       smallest grids the 8 KiB / 32 KiB tiles are used for
+ *   UTM_TILE_STEPS (0; {0, 2, 4, 8, 16, 32})  force the covered tile to 32/16/8/4/2 KiB (0: by the grid)
+ *   UTM_NT_LOADS (-1; -1..1)                 non-temporal column loads on/off (-1: by the matrix size)
+ *   UTM_NT_MIN_MB (512; 0..2^24)             matrix size from which they are used
+ *   UTM_SCORE_FORM (1; 0..1)                 integer launches at 32 / 16 KiB tiles: 0 = k_score_int (LDS tile), 1 = k_score_intq
+ *   UTM_FUSE_PICK (1; 0..1)                  pick inside the scoring launch (one shard or mailbox exchange, integer scores)
+ *   UTM_CHAIN_PICK (1; 0..1)                 AF with candidate chains: pick inside the chain launch (one shard)
+ *   UTM_AF_VERIFY (1; 0..1)                  ... and candidates, compaction, chains and pick as stages of ONE launch (one shard)
+ *   UTM_AF_RECORD (1; 0..1)                  AF: a chain's float64 sum stays on record per sample for as long as the sample's count does not change
+ *   UTM_AF_DEFER (1; 0..1)                   AF, one shard: exact float64 scores of unambiguous winners are finished per batch from a
  *                             log of newly-covered masks (needs 64 columns + 8 bytes per variant of HBM; 0: chained on the spot)
- *   UTM_PICK_THREADS (auto)   threads of the stand-alone k_pick             UTM_BATCH (256; AF 64) iterations between host syncs
- *   UTM_AF_STEPS (16), UTM_AF_SWITCH (0.2), UTM_AF_TARGET_WGS (16384)       AF kernels: tile, dense->streaming switch, grid
- *   UTM_AF_TABLES (1)         the full dense AF pass as table lookups (k_score_aft) where every fixed-point value is below 2^45; 0: k_score_afq
- *   UTM_AF_TABLE_WGS_PER_CU (8), UTM_AF_TABLE_RUN (0 = by the grid)         ... its grid: workgroups per CU, or tiles per workgroup outright
- *   UTM_AF_DENSE_DELTA (0.05) AF delta passes take the LDS-tile kernel while the last winner newly covered more than this share of all variants
- *   UTM_DECR_FIRST_BATCH (8), UTM_DECR_INTERLEAVED (1)                      decremental mode: first batch size, second copy on/off
- *   UTM_P2P_REPLICATE (1)     copy the peers' columns once (0: read winners in place over the mappings)
- *   UTM_TEST_REMOTE_WINNER (0) test hook: read local winners from the exchange's winner-column buffer too
- *   UTM_PERSISTENT (1)        integer scores (weighted or not) and the verified-parallel AF forms, one chunk, the only shard: a
+ *   UTM_PICK_THREADS (0; 0..1024 step 64)    threads of the stand-alone k_pick (0: by the sample count)
+ *   UTM_BATCH (0; 0..65536)                  iterations between host syncs (0: 256; AF 64)
+ *   UTM_AF_STEPS (16; {16, 32}), UTM_AF_SWITCH (0.2; 0..2), UTM_AF_TARGET_WGS (16384; 1..2^24)   AF kernels: tile, dense->streaming switch, grid
+ *   UTM_AF_TABLES (1; 0..1)                  the full dense AF pass as table lookups (k_score_aft) where every fixed-point value is below 2^45; 0: k_score_afq
+ *   UTM_AF_TABLE_WGS_PER_CU (8; 1..1024), UTM_AF_TABLE_RUN (0; 0..65536)   ... its grid: workgroups per CU, or tiles per workgroup outright (0: by the grid)
+ *   UTM_AF_DENSE_DELTA (0.05; 0..2)          AF delta passes take the LDS-tile kernel while the last winner newly covered more than this share of all variants
+ *   UTM_DECR_FIRST_BATCH (8; 1..65536), UTM_DECR_INTERLEAVED (1; 0..1)   decremental mode: first batch size, second copy on/off
+ *   UTM_P2P_REPLICATE (1; 0..1)              copy the peers' columns once (0: read winners in place over the mappings)
+ *   UTM_TEST_REMOTE_WINNER (0; 0..1)         test hook: read local winners from the exchange's winner-column buffer too
+ *   UTM_PERSISTENT (1; 0..1)                 integer scores (weighted or not) and the verified-parallel AF forms, one chunk, the only shard: a
  *                             batch of iterations as ONE persistent
  *                             launch (k_loop_int: workers keep their covered tile in LDS, the picker's record replaces the kernel
  *                             boundary, two batches per wave run ahead across the hand-off)
- *   UTM_PERSIST_MAX_MB (560), UTM_PERSIST_MAX_SAMPLES (2560), UTM_PERSIST_MAX_TILES (32)   largest matrix / sample count run that
- *                             way, and the tile count the tile size (8 / 16 / 32 / 64 KiB) is chosen for; UTM_PERSIST_TILE_KIB forces one;
- *                             tiles above 8 KiB (columns taller than 32 tiles) only up to UTM_PERSIST_TALL_MAX_SAMPLES (640) samples
- *   UTM_PERSIST_WGS_PER_CU (0 = what the occupancy query allows)   resident 512-thread blocks per CU the grid is sized for
- *   UTM_PERSIST_AHEAD_TICKS (400), UTM_PERSIST_AHEAD0_TICKS (0)    10 ns ticks before the next record is due at which a wave requests
- *                             its second / first run-ahead batch (0: as soon as it runs out of work)
- *   UTM_PERSIST_AF (1)        AF scores: the delta iterations run inside the persistent loop too -- float32 AF in its exact fixed-point
- *                             phase, and (UTM_PERSIST_AF_INTERVAL, 1) float64 AF / float32 sums outside the exact range with score intervals:
- *                             the picker lists the candidates, UTM_PERSIST_CHAINERS (4, 1..8) blocks at the end of the grid keep their
- *                             sequential float64 sums on record, working ahead while iterations take longer than UTM_PERSIST_SPEC_TICKS
- *                             (1000 x 10 ns; -1: only on request; -2: test hook, the chainers leave and every request times out).
- *                             Both AF forms: 8 KiB tiles only, at most UTM_PERSIST_AF_MAX_TILES (26)
- *   UTM_PERSIST_CLAIMS (1)    positions behind a wave's two static ones are claimed from per-tile counters (0: dealt statically)
- *   UTM_MBOX_SPINS_LOG2 (24)  mailbox exchange: polls (x ~0.5 us) before a peer's record is declared lost (UTM_ECOMM)
- *   UTM_TEST_MUTE_EXCHANGE (0) test hook: in that iteration since the reset this shard posts no record into the mailboxes
- *   UTM_TEST_DROP_ARRIVAL (0) test hook: in that scoring launch / persistent iteration since the reset one partial count is
+ *   UTM_PERSIST_MAX_MB (560; 0..2^24), UTM_PERSIST_MAX_SAMPLES (2560; 0..2^28), UTM_PERSIST_MAX_TILES (32; 1..4095)   largest matrix /
+ *                             sample count run that way (0: no limit), and the tile count the tile size (8 / 16 / 32 / 64 KiB) is
+ *                             chosen for; UTM_PERSIST_TILE_KIB (0; {0, 8, 16, 32, 64}) forces one; tiles above 8 KiB (columns taller
+ *                             than 32 tiles) only up to UTM_PERSIST_TALL_MAX_SAMPLES (640; 0..2^28) samples.  A tile grid of more
+ *                             tiles than the loop's arrival fields count (4,095; the AF forms 255) always keeps the launches
+ *   UTM_PERSIST_WGS_PER_CU (0; 0..16)        resident 512-thread blocks per CU the grid is sized for (0: what the occupancy query allows)
+ *   UTM_PERSIST_AHEAD_TICKS (400; 0..2^30), UTM_PERSIST_AHEAD0_TICKS (0; 0..2^30)   10 ns ticks before the next record is due at which a
+ *                             wave requests its second / first run-ahead batch (0: as soon as it runs out of work)
+ *   UTM_PERSIST_AF (1; 0..1)                 AF scores: the delta iterations run inside the persistent loop too -- float32 AF in its exact fixed-point
+ *                             phase, and (UTM_PERSIST_AF_INTERVAL (1; 0..1)) float64 AF / float32 sums outside the exact range with score
+ *                             intervals: the picker lists the candidates, UTM_PERSIST_CHAINERS (4; 1..8) blocks at the end of the grid
+ *                             keep their sequential float64 sums on record, working ahead while iterations take longer than
+ *                             UTM_PERSIST_SPEC_TICKS (1000; -2..2^30) x 10 ns (-1: only on request; -2: test hook, the chainers leave
+ *                             and every request times out).  Both AF forms: 8 KiB tiles only, at most UTM_PERSIST_AF_MAX_TILES (26; 1..255)
+ *   UTM_PERSIST_CLAIMS (1; 0..1)             positions behind a wave's two static ones are claimed from per-tile counters (0: dealt statically)
+ *   UTM_MBOX_SPINS_LOG2 (24; 4..28)          mailbox exchange: polls (x ~0.5 us) before a peer's record is declared lost (UTM_ECOMM)
+ *   UTM_TEST_MUTE_EXCHANGE (0; 0..INT_MAX)   test hook: in that iteration since the reset this shard posts no record into the mailboxes
+ *   UTM_TEST_DROP_ARRIVAL (0; 0..INT_MAX)    test hook: in that scoring launch / persistent iteration since the reset one partial count is
  *                             withheld, so that the pick's bounded wait runs out (UTM_EHIP; the context works again after utm_reset)
  */
 #ifndef UTMOS_HIP_H

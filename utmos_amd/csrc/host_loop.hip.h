@@ -261,6 +261,7 @@ static LoopShape loop_shape(utm_ctx *c, int af = 0)
         const int steps = 8 << t;
         if (tn.persist_tile_kib > 0 && steps != tn.persist_tile_kib) continue;
         const u64 tiles = (steps_total + steps - 1) / steps;
+        if (tiles > (af ? UTM_LOOP_MAX_TILES_AF : UTM_LOOP_MAX_TILES_INT)) continue;  // (more than the arrival fields count: even a forced tile)
         if (tiles > (u64)std::max(1, tn.persist_max_tiles) && tn.persist_tile_kib <= 0) continue;
         // The AF forms: the one-batch tile only, and fewer tiles -- their workers keep two tiles in LDS and gather, their
         // words travel in pairs.  Measured against the launches (2,504 samples, float32 / float64 AF): 17 tiles +23 % /

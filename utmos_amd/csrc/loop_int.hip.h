@@ -94,6 +94,13 @@ static_assert(sizeof(LoopSync) % 16 == 0, "zeroed by one memset");
 #endif
 #define UTM_NONEMPTY_SHIFT 52
 #define UTM_AFD_ARRIVAL_SHIFT 56
+// The most tiles one launch can count: the count word's arrival field (bits UTM_ARRIVAL_SHIFT ..) and, in the AF forms,
+// the sum word's arrival field (8 bits).  loop_shape keeps taller tile grids on the launches, whatever the knobs say.
+constexpr unsigned UTM_LOOP_MAX_TILES_INT = (1u << (UTM_NONEMPTY_SHIFT - UTM_ARRIVAL_SHIFT)) - 1;
+constexpr unsigned UTM_LOOP_MAX_TILES_AF = (1u << (64 - UTM_AFD_ARRIVAL_SHIFT)) - 1 < UTM_LOOP_MAX_TILES_INT
+                                               ? (1u << (64 - UTM_AFD_ARRIVAL_SHIFT)) - 1 : UTM_LOOP_MAX_TILES_INT;
+static_assert(UTM_NONEMPTY_SHIFT - UTM_ARRIVAL_SHIFT == 12, "the count word holds a 12-bit arrival field");
+static_assert(UTM_LOOP_MAX_TILES_AF == 255, "the AF forms' sum word holds an 8-bit arrival field");
 #define UTM_COLS_SLACK_BYTES (64u << 10)  // zeros behind a chunk's last column (whole-batch reads of a short last tile)
 #define UTM_LOOP_EPOCH_MASK 0xFFFFFFull
 #define UTM_LOOP_MAX_LOCAL (1u << 28)    // best_pos / moved are 28-bit fields
@@ -554,7 +561,7 @@ __device__ __forceinline__ void loop_picker(const PickArgs &a, LoopSync *sync, u
                     v[e] = (need >> e & 1) ? __hip_atomic_fetch_add(words + e * UTM_LOOP_THREADS, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
 #pragma unroll
                 for (int e = 0; e < UTM_LOOP_E; ++e) {
-                    bool fin = (need >> e & 1) && ((v[e] >> UTM_ARRIVAL_SHIFT) & 0xFFFu) == n_tiles;
+                    bool fin = (need >> e & 1) && ((v[e] >> UTM_ARRIVAL_SHIFT) & UTM_LOOP_MAX_TILES_INT) == n_tiles;
                     u64 d_af = 0;
                     if (AF && fin && (v[e] >> UTM_NONEMPTY_SHIFT)) {
                         // the sum word: complete when it shows as many arrivals as the count word announces (else next round)

@@ -7,14 +7,17 @@
 #include "../../include/utmos_hip.h"
 
 #include <dlfcn.h>
+#include <errno.h>
 #include <hip/hip_ext.h>
 #include <math.h>
 #include <rccl/rccl.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 #include "kernels.hip.h"
@@ -130,67 +133,96 @@ struct Tune {
     int persistent, persist_max_mb, persist_wgs_per_cu, persist_claims, persist_ahead_ticks, persist_ahead0_ticks, persist_max_tiles, persist_tile_kib, persist_max_samples, persist_tall_max_samples, persist_af, persist_af_max_tiles, persist_af_interval, persist_spec_ticks, persist_chainers, test_drop_arrival;
     int mbox_spins_log2, test_mute_exchange;                                 // mailbox exchange: patience, test hook   // persistent loop kernel
 };
+// Every knob has the range its code can honour: lo..hi (and a multiple of step), or one of the values listed in `set`.
+// A value outside it -- or one that is not a number -- leaves the default in place (read_tune); the first context of a
+// process names it on stderr (report_env_once).
 struct KnobDef {
     const char *name;
     int is_double;
     size_t offset;
-    double dflt;
+    double dflt, lo, hi;
+    int step;         // integer knobs: the value is a multiple of this
+    const char *set;  // or, when set, one of these (blank-separated)
 };
-#define UTM_KNOB_I(env, field, dflt) {env, 0, offsetof(Tune, field), (double)(dflt)}
-#define UTM_KNOB_D(env, field, dflt) {env, 1, offsetof(Tune, field), (double)(dflt)}
+#define UTM_KNOB_I(env, field, dflt, lo, hi) {env, 0, offsetof(Tune, field), (double)(dflt), (double)(lo), (double)(hi), 1, nullptr}
+#define UTM_KNOB_STEP(env, field, dflt, lo, hi, step) {env, 0, offsetof(Tune, field), (double)(dflt), (double)(lo), (double)(hi), step, nullptr}
+#define UTM_KNOB_SET(env, field, dflt, set) {env, 0, offsetof(Tune, field), (double)(dflt), 0.0, 0.0, 1, set}
+#define UTM_KNOB_D(env, field, dflt, lo, hi) {env, 1, offsetof(Tune, field), (double)(dflt), (double)(lo), (double)(hi), 1, nullptr}
 static const KnobDef g_knobs[] = {
-    UTM_KNOB_I("UTM_TARGET_WGS", target_wgs, 32768),
-    UTM_KNOB_I("UTM_MIN_WGS", min_wgs, 128),          // (1024 before the pick moved into the launch: 8 KiB tiles now win down to the last iterations)
-    UTM_KNOB_I("UTM_MIN_WGS_BIG", min_wgs_big, 8192), // the 32 KiB tile wants a deeper grid (chr22-sized: +17 % with 8 KiB)
-    UTM_KNOB_I("UTM_TILE_STEPS", tile_steps, 0),
-    UTM_KNOB_I("UTM_NT_LOADS", nt_loads, -1),
-    UTM_KNOB_I("UTM_NT_MIN_MB", nt_min_mb, 512),
-    UTM_KNOB_I("UTM_SCORE_FORM", score_form, 1),      // integer launches at 32 / 16 KiB tiles: 0 = k_score_int (LDS tile), 1 = k_score_intq (tile quarters in registers)
-    UTM_KNOB_I("UTM_FUSE_PICK", fuse_pick, 1),
-    UTM_KNOB_I("UTM_PICK_THREADS", pick_threads, 0),
-    UTM_KNOB_I("UTM_BATCH", batch, 0),
-    UTM_KNOB_I("UTM_AF_STEPS", af_steps, 16),
-    UTM_KNOB_I("UTM_AF_TARGET_WGS", af_target_wgs, 16384),
-    UTM_KNOB_I("UTM_AF_TABLE_RUN", af_table_run, 0),  // ... tiles per workgroup (0: by the grid, about UTM_AF_TABLE_WGS_PER_CU workgroups per CU)
-    UTM_KNOB_I("UTM_AF_TABLE_WGS_PER_CU", af_table_wgs_per_cu, 8),  // (10M x 2,504, same box: 2 -> 1,121 us, 4 -> 951, 8 -> 842, 12 -> 867, 16 -> 921, 24 -> 974)
-    UTM_KNOB_I("UTM_AF_TABLES", af_tables, 1),  // full dense AF passes as table lookups (k_score_aft) where the table admits it; 0: k_score_afq
-    UTM_KNOB_I("UTM_CHAIN_PICK", chain_pick, 1),
-    UTM_KNOB_I("UTM_AF_VERIFY", af_verify, 1),
-    UTM_KNOB_I("UTM_AF_RECORD", af_record, 1),
-    UTM_KNOB_I("UTM_AF_DEFER", af_defer, 1),
-    UTM_KNOB_D("UTM_AF_SWITCH", af_switch, 0.2),
-    UTM_KNOB_D("UTM_AF_DENSE_DELTA", af_dense_delta, 0.05),
-    UTM_KNOB_I("UTM_DECR_FIRST_BATCH", decr_first_batch, 8),
-    UTM_KNOB_I("UTM_DECR_INTERLEAVED", decr_interleaved, 1),
-    UTM_KNOB_I("UTM_P2P_REPLICATE", p2p_replicate, 1),
-    UTM_KNOB_I("UTM_TEST_REMOTE_WINNER", test_remote_winner, 0),
-    UTM_KNOB_I("UTM_PERSISTENT", persistent, 1),
-    UTM_KNOB_I("UTM_PERSIST_MAX_MB", persist_max_mb, 560),  // (2,504 samples, same box, against the launches with 8 KiB tiles: +5 % at 0.47 GB, +0.5 % at 0.63 GB, -3.4 ... +2 % at 0.94 GB, -2.6 % at 1.56 GB; with their 16 KiB tiles from 1.8M variants up the launches lead by 2 % at 0.63 GB = 599 MiB, so the limit sits below that)
-    UTM_KNOB_I("UTM_PERSIST_WGS_PER_CU", persist_wgs_per_cu, 0),
-    UTM_KNOB_I("UTM_PERSIST_MAX_TILES", persist_max_tiles, 32),
-    UTM_KNOB_I("UTM_PERSIST_TILE_KIB", persist_tile_kib, 0),
-    UTM_KNOB_I("UTM_PERSIST_TALL_MAX_SAMPLES", persist_tall_max_samples, 640),  // tiles of several batches (columns taller than 32 x 8 KiB) only up to this many samples
-    UTM_KNOB_I("UTM_PERSIST_MAX_SAMPLES", persist_max_samples, 2560),  // (one chunk of count words for the picker: UTM_LOOP_THREADS x UTM_LOOP_E)
-    UTM_KNOB_I("UTM_PERSIST_AF", persist_af, 1),  // the AF form (exact float32 phase) of the persistent loop
-    UTM_KNOB_I("UTM_PERSIST_AF_MAX_TILES", persist_af_max_tiles, 26),  // ... both AF forms: 8 KiB tiles only, at most this many (taller matrices keep the launches)
-    UTM_KNOB_I("UTM_PERSIST_SPEC_TICKS", persist_spec_ticks, 1000),  // interval form: the chainer works ahead (one chain per record) while iterations take longer than this many 10 ns ticks -- a request waits for a chain in progress; -1: never; -2 (test hook): the chainers leave at once, every request times out and the host decides
-    UTM_KNOB_I("UTM_PERSIST_CHAINERS", persist_chainers, 4),  // interval form: blocks that keep sequential float64 sums on record (1..8; a request for 2 x this many samples is served in one go)
-    UTM_KNOB_I("UTM_PERSIST_AF_INTERVAL", persist_af_interval, 1),  // ... and its interval form (float64 AF values; float32 sums outside the exact range): candidates and chains inside the picker
-    UTM_KNOB_I("UTM_PERSIST_CLAIMS", persist_claims, 1),
-    UTM_KNOB_I("UTM_PERSIST_AHEAD0_TICKS", persist_ahead0_ticks, 0),
-    UTM_KNOB_I("UTM_PERSIST_AHEAD_TICKS", persist_ahead_ticks, 400),  // 10 ns ticks: the second run-ahead batch goes out this long before the record is due (0: at once)
-    UTM_KNOB_I("UTM_TEST_DROP_ARRIVAL", test_drop_arrival, 0),
-    UTM_KNOB_I("UTM_MBOX_SPINS_LOG2", mbox_spins_log2, 24),
-    UTM_KNOB_I("UTM_TEST_MUTE_EXCHANGE", test_mute_exchange, 0),
+    UTM_KNOB_I("UTM_TARGET_WGS", target_wgs, 32768, 1, 1 << 24),
+    UTM_KNOB_I("UTM_MIN_WGS", min_wgs, 128, 0, 1 << 24),          // (1024 before the pick moved into the launch: 8 KiB tiles now win down to the last iterations)
+    UTM_KNOB_I("UTM_MIN_WGS_BIG", min_wgs_big, 8192, 0, 1 << 24), // the 32 KiB tile wants a deeper grid (chr22-sized: +17 % with 8 KiB)
+    UTM_KNOB_SET("UTM_TILE_STEPS", tile_steps, 0, "0 2 4 8 16 32"),
+    UTM_KNOB_I("UTM_NT_LOADS", nt_loads, -1, -1, 1),
+    UTM_KNOB_I("UTM_NT_MIN_MB", nt_min_mb, 512, 0, 1 << 24),
+    UTM_KNOB_I("UTM_SCORE_FORM", score_form, 1, 0, 1),      // integer launches at 32 / 16 KiB tiles: 0 = k_score_int (LDS tile), 1 = k_score_intq (tile quarters in registers)
+    UTM_KNOB_I("UTM_FUSE_PICK", fuse_pick, 1, 0, 1),
+    UTM_KNOB_STEP("UTM_PICK_THREADS", pick_threads, 0, 0, 1024, 64),
+    UTM_KNOB_I("UTM_BATCH", batch, 0, 0, 65536),
+    UTM_KNOB_SET("UTM_AF_STEPS", af_steps, 16, "16 32"),
+    UTM_KNOB_I("UTM_AF_TARGET_WGS", af_target_wgs, 16384, 1, 1 << 24),
+    UTM_KNOB_I("UTM_AF_TABLE_RUN", af_table_run, 0, 0, 65536),  // ... tiles per workgroup (0: by the grid, about UTM_AF_TABLE_WGS_PER_CU workgroups per CU)
+    UTM_KNOB_I("UTM_AF_TABLE_WGS_PER_CU", af_table_wgs_per_cu, 8, 1, 1024),  // (10M x 2,504, same box: 2 -> 1,121 us, 4 -> 951, 8 -> 842, 12 -> 867, 16 -> 921, 24 -> 974)
+    UTM_KNOB_I("UTM_AF_TABLES", af_tables, 1, 0, 1),  // full dense AF passes as table lookups (k_score_aft) where the table admits it; 0: k_score_afq
+    UTM_KNOB_I("UTM_CHAIN_PICK", chain_pick, 1, 0, 1),
+    UTM_KNOB_I("UTM_AF_VERIFY", af_verify, 1, 0, 1),
+    UTM_KNOB_I("UTM_AF_RECORD", af_record, 1, 0, 1),
+    UTM_KNOB_I("UTM_AF_DEFER", af_defer, 1, 0, 1),
+    UTM_KNOB_D("UTM_AF_SWITCH", af_switch, 0.2, 0, 2),
+    UTM_KNOB_D("UTM_AF_DENSE_DELTA", af_dense_delta, 0.05, 0, 2),
+    UTM_KNOB_I("UTM_DECR_FIRST_BATCH", decr_first_batch, 8, 1, 65536),
+    UTM_KNOB_I("UTM_DECR_INTERLEAVED", decr_interleaved, 1, 0, 1),
+    UTM_KNOB_I("UTM_P2P_REPLICATE", p2p_replicate, 1, 0, 1),
+    UTM_KNOB_I("UTM_TEST_REMOTE_WINNER", test_remote_winner, 0, 0, 1),
+    UTM_KNOB_I("UTM_PERSISTENT", persistent, 1, 0, 1),
+    UTM_KNOB_I("UTM_PERSIST_MAX_MB", persist_max_mb, 560, 0, 1 << 24),  // (2,504 samples, same box, against the launches with 8 KiB tiles: +5 % at 0.47 GB, +0.5 % at 0.63 GB, -3.4 ... +2 % at 0.94 GB, -2.6 % at 1.56 GB; with their 16 KiB tiles from 1.8M variants up the launches lead by 2 % at 0.63 GB = 599 MiB, so the limit sits below that)
+    UTM_KNOB_I("UTM_PERSIST_WGS_PER_CU", persist_wgs_per_cu, 0, 0, 16),
+    UTM_KNOB_I("UTM_PERSIST_MAX_TILES", persist_max_tiles, 32, 1, UTM_LOOP_MAX_TILES_INT),
+    UTM_KNOB_SET("UTM_PERSIST_TILE_KIB", persist_tile_kib, 0, "0 8 16 32 64"),
+    UTM_KNOB_I("UTM_PERSIST_TALL_MAX_SAMPLES", persist_tall_max_samples, 640, 0, UTM_LOOP_MAX_LOCAL),  // tiles of several batches (columns taller than 32 x 8 KiB) only up to this many samples
+    UTM_KNOB_I("UTM_PERSIST_MAX_SAMPLES", persist_max_samples, 2560, 0, UTM_LOOP_MAX_LOCAL),  // (one chunk of count words for the picker: UTM_LOOP_THREADS x UTM_LOOP_E)
+    UTM_KNOB_I("UTM_PERSIST_AF", persist_af, 1, 0, 1),  // the AF form (exact float32 phase) of the persistent loop
+    UTM_KNOB_I("UTM_PERSIST_AF_MAX_TILES", persist_af_max_tiles, 26, 1, UTM_LOOP_MAX_TILES_AF),  // ... both AF forms: 8 KiB tiles only, at most this many (taller matrices keep the launches)
+    UTM_KNOB_I("UTM_PERSIST_SPEC_TICKS", persist_spec_ticks, 1000, -2, 1 << 30),  // interval form: the chainer works ahead (one chain per record) while iterations take longer than this many 10 ns ticks -- a request waits for a chain in progress; -1: never; -2 (test hook): the chainers leave at once, every request times out and the host decides
+    UTM_KNOB_I("UTM_PERSIST_CHAINERS", persist_chainers, 4, 1, UTM_LOOP_MAX_CHAINERS),  // interval form: blocks that keep sequential float64 sums on record (1..8; a request for 2 x this many samples is served in one go)
+    UTM_KNOB_I("UTM_PERSIST_AF_INTERVAL", persist_af_interval, 1, 0, 1),  // ... and its interval form (float64 AF values; float32 sums outside the exact range): candidates and chains inside the picker
+    UTM_KNOB_I("UTM_PERSIST_CLAIMS", persist_claims, 1, 0, 1),
+    UTM_KNOB_I("UTM_PERSIST_AHEAD0_TICKS", persist_ahead0_ticks, 0, 0, 1 << 30),
+    UTM_KNOB_I("UTM_PERSIST_AHEAD_TICKS", persist_ahead_ticks, 400, 0, 1 << 30),  // 10 ns ticks: the second run-ahead batch goes out this long before the record is due (0: at once)
+    UTM_KNOB_I("UTM_TEST_DROP_ARRIVAL", test_drop_arrival, 0, 0, INT_MAX),
+    UTM_KNOB_I("UTM_MBOX_SPINS_LOG2", mbox_spins_log2, 24, 4, 28),
+    UTM_KNOB_I("UTM_TEST_MUTE_EXCHANGE", test_mute_exchange, 0, 0, INT_MAX),
 };
+// The value of a knob's environment text, or false when it is not a number in the knob's range.
+static bool knob_parse(const KnobDef &k, const char *v, double *out)
+{
+    char *end = nullptr;
+    errno = 0;
+    const double d = k.is_double ? strtod(v, &end) : (double)strtoll(v, &end, 10);
+    if (end == v || *end || errno || !isfinite(d)) return false;
+    if (k.set) {
+        for (const char *p = k.set; *p;) {
+            char *e = nullptr;
+            const long x = strtol(p, &e, 10);
+            if (e == p) break;
+            if ((double)x == d) return *out = d, true;
+            p = e;
+        }
+        return false;
+    }
+    if (d < k.lo || d > k.hi || (!k.is_double && (long long)d % k.step != 0)) return false;
+    *out = d;
+    return true;
+}
 static void read_tune(Tune *t)
 {
     for (const KnobDef &k : g_knobs) {
         const char *v = getenv(k.name);
-        const bool set = v && *v;
+        double d = k.dflt;
+        if (v && *v) (void)knob_parse(k, v, &d);  // (an illegal value keeps the default)
         char *at = reinterpret_cast<char *>(t) + k.offset;
-        if (k.is_double) *reinterpret_cast<double *>(at) = set ? atof(v) : k.dflt;
-        else *reinterpret_cast<int *>(at) = set ? atoi(v) : (int)k.dflt;
+        if (k.is_double) *reinterpret_cast<double *>(at) = d;
+        else *reinterpret_cast<int *>(at) = (int)d;
     }
 }
 // " NAME=value" for every knob that is set in the environment; returns the number of characters written.
@@ -403,6 +435,11 @@ static void report_env_once()
     said = true;
     char line[1024];
     if (format_env_overrides(line, sizeof line)) fprintf(stderr, "libutmos_hip: environment overrides in effect: %s\n", line);
+    for (const KnobDef &k : g_knobs) {
+        const char *v = getenv(k.name);
+        double d;
+        if (v && *v && !knob_parse(k, v, &d)) fprintf(stderr, "libutmos_hip: %s=%.24s is outside its range: ignored, the default holds\n", k.name, v);
+    }
 }
 
 extern "C" int utm_ctx_create(int device, uint32_t n_samp_total, uint32_t first_sample, uint32_t n_samp_local,
