@@ -383,6 +383,45 @@ int utm_deflate_timing(utm_deflate *deflate, double *ms);
 int utm_deflate_host(const uint8_t *in, uint64_t n_bytes, int level, uint8_t *out, uint64_t out_cap,
                      uint64_t *out_bytes, uint32_t *adler);
 
+/* ---- HDF5 store chunks (no utm_ctx) ------------------------------------------------------------ */
+/* The `data` dataset of the reference's `--lowmem` store (utmos/select.py:198-229): chunks of whole rows, every column,
+ * LZF-compressed by h5py (filter 32000) or stored raw, cells of one byte (bool / int8 / uint8) or four (float32
+ * GT * AF).  utmos_amd/h5store.py reads the file's structure; the chunks are decoded and packed on the device
+ * (csrc/lzf.hip.h).  A context is made for one dataset's chunk shape (chunk_rows x n_cols cells of itemsize bytes)
+ * and holds two batch slots, each with its own stream, so the host reads one batch from the file while the GPU
+ * decodes the other. */
+#define UTM_H5_MAX_STAGE 2147479552ull        /* 2^31 - 4096 stored bytes per batch */
+#define UTM_H5_MAX_CHUNKS 65536u              /* chunks per batch */
+#define UTM_H5_MAX_CHUNK_BYTES 2147418112ull  /* 2^31 - 2^16 decoded bytes per chunk */
+#define UTM_LZF_E_INPUT 1                     /* chunk status: a token runs past the stored bytes */
+#define UTM_LZF_E_OUTPUT 2                    /* ... more output than the chunk holds (a raw chunk: larger than it) */
+#define UTM_LZF_E_SHORT 3                     /* ... less output than the chunk holds (a raw chunk: smaller than it) */
+#define UTM_LZF_E_BACKREF 4                   /* ... a back-reference before the start of the chunk */
+#define UTM_H5_E_VALUES 5                     /* ... float32: a row's nonzero cells differ, or one is negative or NaN */
+typedef struct utm_h5 utm_h5;
+int utm_h5_create(int device, uint64_t stage_bytes, uint32_t max_chunks, uint32_t chunk_rows, uint32_t n_cols,
+                  uint32_t itemsize, utm_h5 **out);
+int utm_h5_destroy(utm_h5 *h5);
+/* The pinned staging buffer (*cap = stage_bytes): a caller may read a batch into it and pass it to utm_h5_decode. */
+int utm_h5_staging(utm_h5 *h5, uint8_t **buf, uint64_t *cap);
+/* Queue one batch of n_chunks chunks: chunk i's stored bytes are in[offsets[i], offsets[i] + sizes[i]) (any
+ * alignment; `in` is the staging, no copy, or any host memory), masks[i] its HDF5 filter mask (bit 0: stored raw, then
+ * sizes[i] must be the chunk's decoded size), rows[i] its rows below the end of the dataset, which are packed
+ * (a partial last chunk is stored full size).  sizes[i] == 0: the chunk is absent and reads as zeros.  Returns once
+ * the batch is on the device and the kernels are queued (the staging may be filled again).  At most two batches wait
+ * for utm_h5_fetch. */
+int utm_h5_decode(utm_h5 *h5, const uint8_t *in, uint64_t n_bytes, const uint64_t *offsets, const uint64_t *sizes,
+                  const uint32_t *masks, const uint32_t *rows, uint32_t n_chunks);
+/* Wait for the oldest batch and copy out: rows[sum(rows) * ceil(n_cols / 8)] in numpy.packbits order (cell 0 = MSB of
+ * byte 0), for itemsize 4 af[sum(rows)] (the row's common nonzero value, 0 for an all-zero row), and status[n_chunks]
+ * (0 or UTM_LZF_E_* / UTM_H5_E_VALUES; the rows of a chunk whose status is not 0 are undefined). */
+int utm_h5_fetch(utm_h5 *h5, uint8_t *rows, float *af, uint32_t *status);
+/* HIP-event time summed over the fetched batches: ms[0] host-to-device, ms[1] decode, ms[2] pack, ms[3] device-to-host. */
+int utm_h5_timing(utm_h5 *h5, double *ms);
+/* The device's LZF decoder built for the CPU: one chunk in[0, n_in) -> out[0, n_out).  *status = 0 when it decodes to
+ * exactly n_out bytes, else a UTM_LZF_E_* code (out is then partly written).  Needs no GPU. */
+int utm_lzf_decode_host(const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t n_out, uint32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

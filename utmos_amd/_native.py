@@ -108,6 +108,13 @@ PROTOTYPES = {
     "utm_deflate_adler": [_P, ctypes.POINTER(_U32)],
     "utm_deflate_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_deflate_host": [_P, _U64, ctypes.c_int, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U32)],
+    "utm_h5_create": [ctypes.c_int, _U64, _U32, _U32, _U32, _U32, ctypes.POINTER(_P)],
+    "utm_h5_destroy": [_P],
+    "utm_h5_staging": [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64)],
+    "utm_h5_decode": [_P, _P, _U64, _P, _P, _P, _P, _U32],
+    "utm_h5_fetch": [_P, _P, _P, _P],
+    "utm_h5_timing": [_P, ctypes.POINTER(ctypes.c_double)],
+    "utm_lzf_decode_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U32)],
 }
 
 _lib = None

@@ -14,3 +14,4 @@
 #include "vcf.hip.h"
 #include "inflate.hip.h"
 #include "deflate.hip.h"
+#include "lzf.hip.h"

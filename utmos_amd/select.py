@@ -29,6 +29,8 @@ MAXMEM = 2  # GB one HBM chunk of packed columns may take; 0 = smallest chunks (
 
 HEADER = "sample\tvar_count\tnew_count\ttot_captured\tpct_captured\n"
 
+H5_SUFFIX = ".hdf5"                      # the reference's --lowmem store, read here (h5store.py), never written
+
 SELECTABLE, USED, EXCLUDED = 1, 0, 2      # sample_mask values (select.py:168: "1 = can use, 0 = mask, 2 = exclude")
 
 
@@ -228,6 +230,61 @@ class _ChunkBuilder:
         self.chunk_af.append(af)
 
 
+def _place_part(builder, rows, af, n_samples, calc_af, buffer):
+    """Hand one part's packed rows to the chunk builder: parts are merged while the chunk stays within --maxmem; a part
+    too large for one chunk is cut into the largest pieces that fit; `buffer` variants per chunk only when chunking is
+    forced (--maxmem 0): chunks are HBM allocations here, not the I/O granularity they are for the reference's hdf5
+    appends."""
+    if MAXMEM != 0 and is_memsafe((len(rows), n_samples), calc_af):
+        if builder.held_variants() and not is_memsafe((builder.held_variants() + len(rows), n_samples), calc_af):
+            builder.flush()
+        builder.add(rows, af)
+        return
+    builder.flush()
+    if MAXMEM != 0:
+        per_variant = n_samples / 8 + (8 if calc_af else 0)
+        step = max(64, int(MAXMEM * 1e9 / per_variant) // 64 * 64 - 64)
+    else:
+        step = max(64, buffer // 64 * 64)
+    for lo in range(0, len(rows), step):
+        builder.add(rows[lo:lo + step], af[lo:lo + step])
+        builder.flush()
+
+
+def load_h5(path, dev=0, shard=None, buffer=32768):
+    """Read the reference's `--lowmem` HDF5 store (h5store.py): its `data` chunks are LZF-decoded and packed on the GPU
+    and go through the same chunk builder and upload as the rows of part files.  Unlike part files, all-zero rows stay
+    (the reference's variant total is data.shape[0]) and var_count comes from the file (in an AF store a carrier whose
+    AF is 0 holds 0)."""
+    from .h5store import ChunkDecoder, H5Store
+    try:
+        store = H5Store(path)
+    except (OSError, ValueError) as err:
+        logging.error("%s", err)
+        sys.exit(1)
+    n_var, n_samples = store.data.shape
+    has_af = store.data.kind == "float"
+    logging.info("%s: hdf5 store of %d x %d %s cells in %d chunks", path, n_var, n_samples, store.data.dtype,
+                 len(store.data.chunks))
+    matrix = _shard_matrix(n_samples, dev, shard)
+    builder = _ChunkBuilder(matrix, None, has_af, True)
+    try:
+        with ChunkDecoder(store, dev) as decoder:
+            for _first, rows, af in decoder:
+                _place_part(builder, rows, af if has_af else np.zeros(len(rows), np.float32), n_samples, has_af, buffer)
+            builder.flush()
+            logging.debug("hdf5 decode (ms): %s", decoder.timing())
+    except ValueError as err:
+        matrix.close()
+        logging.error("%s", err)
+        sys.exit(1)
+    if has_af:
+        for chunk, af in enumerate(builder.chunk_af):
+            matrix.set_af(chunk, np.asarray(af, dtype=np.float32))
+    lo, n_local = matrix.first_sample, matrix.n_local
+    return {"samples": store.samples, "data": matrix, "var_count": store.var_count[lo:lo + n_local], "has_af": has_af}
+
+
 def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto"):
     """Load and concatenate the inputs into one HBM-resident matrix -> {"samples", "data", "var_count", "has_af"}.
 
@@ -238,6 +295,8 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
     """
     logging.info("reading %d input file(s)", len(in_files))
     if lowmem == 1:
+        if in_files[0].endswith(H5_SUFFIX):
+            return load_h5(in_files[0], dev, shard, buffer)
         return load_store(in_files[0], dev, shard)
     if shard is not None and shard[1] > 1 and lowmem is not None:
         logging.error("Create the matrix store with a single process, then select from it with several")
@@ -259,24 +318,7 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
         af = np.asarray(part["AF"], dtype=np.float64).reshape(-1)[informative]
         if len(rows) == 0:
             continue
-        if MAXMEM != 0 and is_memsafe((len(rows), len(samples)), calc_af):
-            # parts are merged while the chunk stays within --maxmem
-            if builder.held_variants() and not is_memsafe((builder.held_variants() + len(rows), len(samples)), calc_af):
-                builder.flush()
-            builder.add(rows, af)
-        else:
-            # a part too large for one chunk is cut into the largest pieces that fit; `buffer` variants per chunk only
-            # when chunking is forced (--maxmem 0): chunks are HBM allocations here, not the I/O granularity they are
-            # for the reference's hdf5 appends
-            builder.flush()
-            if MAXMEM != 0:
-                per_variant = len(samples) / 8 + (8 if calc_af else 0)
-                step = max(64, int(MAXMEM * 1e9 / per_variant) // 64 * 64 - 64)
-            else:
-                step = max(64, buffer // 64 * 64)
-            for lo in range(0, len(rows), step):
-                builder.add(rows[lo:lo + step], af[lo:lo + step])
-                builder.flush()
+        _place_part(builder, rows, af, len(samples), calc_af, buffer)
         logging.debug("%d of %d files read", number, len(in_files))
     if builder is not None:
         builder.flush()
@@ -331,7 +373,7 @@ def _build_parser():
     """The option surface of the reference's `utmos select` (flags, defaults and meaning: utmos/select.py:355-398),
     plus this build's --device / --brute-force / --exchange."""
     parser = argparse.ArgumentParser(prog="select", description="Select the fewest samples that capture the most variants (MI355X).")
-    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm store")
+    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm or .hdf5 store")
     parser.add_argument("-c", "--count", type=float, default=0.02,
                         help="how many samples: a fraction of all if < 1, a count if >= 1, every sample if -1 [%(default)s]")
     parser.add_argument("-o", "--out", type=str, default="/dev/stdout", help="TSV destination [stdout]")
@@ -345,7 +387,8 @@ def _build_parser():
                          help="never select these samples (file or comma list; repeatable)")
     memory = parser.add_argument_group("Memory Arguments")
     memory.add_argument("--lowmem", type=str, default=None,
-                        help="packed matrix store (.utm) to write, or to read when no inputs are given")
+                        help="packed matrix store (.utm) to write, or to read (.utm, or the reference's .hdf5) when no "
+                             "inputs are given")
     memory.add_argument("--buffer", type=int, default=32768, help="variants per HBM chunk when chunking is on [%(default)s]")
     memory.add_argument("--maxmem", type=int, default=2, help="GB one chunk may take; 0 = always chunk [%(default)s]")
     gpu = parser.add_argument_group("GPU Arguments")
@@ -365,9 +408,10 @@ def parse_args(args):
     """Parse and validate the command line; exits with status 1 on unusable input combinations (select.py:401-415)."""
     args = _build_parser().parse_args(args)
     setup_logging(args.debug)
-    stores = [name for name in args.in_files if name.endswith((STORE_SUFFIX, ".hdf5"))]
-    if any(name.endswith(".hdf5") for name in args.in_files) or (args.lowmem or "").endswith(".hdf5"):
-        logging.error("hdf5 stores are not read by this build; recreate the store with --lowmem FILE%s", STORE_SUFFIX)
+    stores = [name for name in args.in_files if name.endswith((STORE_SUFFIX, H5_SUFFIX))]
+    if args.in_files and (args.lowmem or "").endswith(H5_SUFFIX):
+        logging.error("hdf5 stores are read, not written, by this build: create the store with --lowmem FILE%s",
+                      STORE_SUFFIX)
         sys.exit(1)
     if stores and len(args.in_files) > 1:
         logging.error("A matrix store cannot be combined with other input files")
