@@ -71,6 +71,25 @@ def test_device_decode_equals_host_on_generated_stores(tmp_path):
     assert np.array_equal(rows, e_rows) and af.tobytes() == e_af.tobytes()
 
 
+def test_slot_errors_leave_the_context_usable():
+    from utmos_amd import _native as nat
+    from utmos_amd.h5store import ChunkDecoder, H5Store
+    lib = nat.lib()
+    with ChunkDecoder(H5Store(TINY), 0) as dec, open(TINY, "rb") as fh:
+        batch = next(dec._plan())
+        assert lib.utm_h5_fetch(dec.h, None, None, None) == -4                          # nothing queued
+        inflight = [dec._submit(fh, batch), dec._submit(fh, batch)]
+        with pytest.raises(nat.NativeError, match="both slots") as err:
+            dec._submit(fh, batch)
+        assert err.value.code == -4
+        e_rows = host_rows(TINY)[0]
+        for k in range(3):
+            _, rows, _ = dec._fetch(*inflight.pop(0))
+            assert len(rows) and np.array_equal(rows, e_rows[:len(rows)])
+            if k == 0:
+                inflight.append(dec._submit(fh, batch))                               # into the freed slot
+
+
 def test_corrupt_chunks_end_in_a_status_not_a_fault(tmp_path):
     from utmos_amd.h5store import H5Store
     s = H5Store(TINY)

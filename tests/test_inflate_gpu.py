@@ -216,6 +216,7 @@ def test_abi_carry_with_prefix_and_a_batch_without_newline():
         return r[:n, 0].tolist()
 
     try:
+        assert lib.utm_vcf_fetch(h, None, None, None, None, None) == -4                   # nothing queued
         got, counts = [], []
         for k, piece in enumerate(pieces):
             members = [bgzf(piece[i:i + 9], eof=False) for i in range(0, len(piece), 9)]
@@ -227,7 +228,9 @@ def test_abi_carry_with_prefix_and_a_batch_without_newline():
             nat.check(lib.utm_vcf_parse_bgzf(h, pre, len(pre) if pre else 0, packed, len(packed), table.ctypes.data,
                                              len(members), flags, ctypes.byref(n_rec), ctypes.byref(carry)))
             counts.append((n_rec.value, carry.value))
-            if k == 1:                       # two batches queued: collect the first
+            if k == 1:                       # two batches queued: a third is refused, then collect the first
+                assert lib.utm_vcf_parse(h, text, len(text), ctypes.byref(n_rec)) == -4
+                assert b"both slots" in lib.utm_last_error()
                 got += fetch(counts[0][0])
         got += fetch(counts[1][0]) + fetch(counts[2][0])
         assert counts == [(2, 7), (0, 12), (2, 0)]

@@ -2,48 +2,32 @@
 // whole 64 KiB segments (the last batch of a stream may end with a shorter one); the caller adds the zlib header and
 // the Adler-32 trailer that utm_deflate_adler combines from the segments' sums.
 //
-// One pinned staging buffer and two slots, each with its own stream, device buffers and pinned output:
+// One pinned staging buffer and two slots (host_batch.hip.h), each with its own device buffers and pinned output:
 // utm_deflate_push returns once its batch has reached the device and the kernels are queued, so the caller fills the
 // staging again while the GPU compresses; utm_deflate_pull collects the oldest batch's bytes.
 #pragma once
 
-struct DefSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[7] = {};  // H2D (0-1), chain + match (1-2), parse (2-3), encode + scan + gather (3-4), D2H (5-6)
-    uint8_t *d_in = nullptr, *d_seg = nullptr, *d_out = nullptr, *h_out = nullptr;
-    uint16_t *d_prev = nullptr;
-    uint32_t *d_match = nullptr, *d_tok = nullptr, *d_ntok = nullptr, *d_sizes = nullptr, *d_offs = nullptr;
-    uint32_t *d_adler = nullptr;
-    uint32_t *h_info = nullptr;  // [0] output bytes of the batch, then (sum, weighted sum) per segment
+struct DefSlot : BatchSlot<7> {  // events: H2D (0-1), chain + match (1-2), parse (2-3), encode + scan + gather (3-4), D2H (5-6)
+    Scratch<uint8_t> d_in, d_seg, d_out;
+    Pinned<uint8_t> h_out;
+    Scratch<uint16_t> d_prev;
+    Scratch<uint32_t> d_match, d_tok, d_ntok, d_sizes, d_offs, d_adler;
+    Pinned<uint32_t> h_info;  // [0] output bytes of the batch, then (sum, weighted sum) per segment
     u64 n = 0;
     uint32_t nseg = 0;
-    bool pending = false, first = false;
+    bool first = false;
 };
 
-struct utm_deflate {
+struct utm_deflate : SlotPair<DefSlot> {
     int device = 0, level = 5;
     u64 batch = 0;
     uint32_t max_seg = 0;
-    uint8_t *h_stage = nullptr;
-    DefSlot slot[2];
-    int next = 0, oldest = 0, n_pending = 0;
+    Pinned<uint8_t> h_stage;
     bool fresh = true;              // the next push starts a stream
     uint32_t a = 1, b = 0;          // Adler-32 halves of the pulled batches of the current stream
     double ms[4] = {0, 0, 0, 0};    // H2D, kernels, D2H, of the kernels the parse
+    ~utm_deflate() { idle(device); }
 };
-
-static void def_slot_free(DefSlot *s)
-{
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->h_info) (void)hipHostFree(s->h_info);
-    void *dev[] = {s->d_in, s->d_seg, s->d_out, s->d_prev, s->d_match, s->d_tok, s->d_ntok, s->d_sizes, s->d_offs, s->d_adler};
-    for (void *d : dev)
-        if (d) (void)hipFree(d);
-    for (hipEvent_t e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    *s = DefSlot();
-}
 
 static u64 def_bound(u64 n) { return n + 15 * std::max<u64>(1, (n + DEF_SEG - 1) / DEF_SEG); }
 
@@ -54,10 +38,6 @@ static void def_adler_add(uint32_t *a, uint32_t *b, u64 len, uint32_t s1, uint32
     *a = (uint32_t)((a0 + s1) % DEF_ADLER_MOD);
     *b = (uint32_t)((*b + (len % DEF_ADLER_MOD) * a0 + s2) % DEF_ADLER_MOD);
 }
-
-#define DEFL(p)                                          \
-    if (!(p)) return fail(UTM_EINVAL, "deflate is NULL"); \
-    HIP_TRY(hipSetDevice((p)->device))
 
 static int def_check_level(int level)
 {
@@ -79,54 +59,35 @@ extern "C" int utm_deflate_create(int device, uint64_t batch_bytes, int level, u
     TRY(def_check_level(level));
     if (batch_bytes == 0 || batch_bytes > UTM_DEFLATE_MAX_BATCH)
         return fail(UTM_EINVAL, "batch_bytes %llu not in [1, 2^30]", (unsigned long long)batch_bytes);
-    int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) return fail(UTM_EINVAL, "device %d of %d", device, n);
-    HIP_TRY(hipSetDevice(device));
-    utm_deflate *p = new utm_deflate();
+    TRY(open_device(device));
+    std::unique_ptr<utm_deflate> p(new utm_deflate());
     p->device = device;
     p->level = level;
     p->max_seg = (uint32_t)((batch_bytes + DEF_SEG - 1) / DEF_SEG);
     p->batch = (u64)p->max_seg * DEF_SEG;
     const u64 nb = p->batch, ns = p->max_seg;
-    hipError_t e = hipHostMalloc((void **)&p->h_stage, nb, hipHostMallocDefault);
+    TRY(p->h_stage.reserve(nb));
     for (DefSlot &s : p->slot) {
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-        for (hipEvent_t &ev : s.ev)
-            if (e == hipSuccess) e = hipEventCreate(&ev);
-        if (e == hipSuccess) e = hipMalloc(&s.d_in, nb + DEF_PAD);
-        if (e == hipSuccess) e = hipMalloc(&s.d_prev, nb * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_match, nb * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_tok, nb * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_seg, ns * DEF_SEG_OUT);
-        if (e == hipSuccess) e = hipMalloc(&s.d_out, def_bound(nb));
-        if (e == hipSuccess) e = hipMalloc(&s.d_ntok, ns * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_sizes, ns * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_offs, (ns + 1) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_adler, 2 * ns * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, def_bound(nb), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_info, (1 + 2 * ns) * sizeof(uint32_t), hipHostMallocDefault);
+        TRY(s.open());
+        TRY(s.d_in.reserve(nb + DEF_PAD));
+        TRY(s.d_prev.reserve(nb));
+        TRY(s.d_match.reserve(nb));
+        TRY(s.d_tok.reserve(nb));
+        TRY(s.d_seg.reserve(ns * DEF_SEG_OUT));
+        TRY(s.d_out.reserve(def_bound(nb)));
+        TRY(s.d_ntok.reserve(ns));
+        TRY(s.d_sizes.reserve(ns));
+        TRY(s.d_offs.reserve(ns + 1));
+        TRY(s.d_adler.reserve(2 * ns));
+        TRY(s.h_out.reserve(def_bound(nb)));
+        TRY(s.h_info.reserve(1 + 2 * ns));
     }
-    if (e != hipSuccess) {
-        const int rc = fail(e == hipErrorOutOfMemory ? UTM_ENOMEM : UTM_EHIP, "utm_deflate_create: %s", hipGetErrorString(e));
-        for (DefSlot &s : p->slot) def_slot_free(&s);
-        if (p->h_stage) (void)hipHostFree(p->h_stage);
-        delete p;
-        return rc;
-    }
-    *out = p;
+    *out = p.release();
     return UTM_OK;
 }
 
 extern "C" int utm_deflate_destroy(utm_deflate *p)
 {
-    if (!p) return UTM_OK;
-    (void)hipSetDevice(p->device);
-    for (DefSlot &s : p->slot) {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        def_slot_free(&s);
-    }
-    if (p->h_stage) (void)hipHostFree(p->h_stage);
     delete p;
     return UTM_OK;
 }
@@ -141,15 +102,15 @@ extern "C" int utm_deflate_staging(utm_deflate *p, uint8_t **buf, uint64_t *cap)
 
 extern "C" int utm_deflate_push(utm_deflate *p, const uint8_t *in, uint64_t n_bytes, uint32_t flags)
 {
-    DEFL(p);
+    BATCH_CTX(p, "deflate");
     if (flags & ~UTM_DEFLATE_LAST) return fail(UTM_EINVAL, "unknown flags 0x%x", flags);
     const bool last = flags & UTM_DEFLATE_LAST;
     if (n_bytes && !in) return fail(UTM_EINVAL, "in is NULL");
     if (n_bytes > p->batch) return fail(UTM_EINVAL, "a batch of %llu bytes (the context takes %llu)", (unsigned long long)n_bytes, (unsigned long long)p->batch);
     if (!last && n_bytes % DEF_SEG)
         return fail(UTM_EINVAL, "a batch of %llu bytes that is not the last must be a multiple of %u", (unsigned long long)n_bytes, DEF_SEG);
-    DefSlot *s = &p->slot[p->next];
-    if (s->pending) return fail(UTM_ESTATE, "both slots hold a batch: utm_deflate_pull first");
+    DefSlot *s;
+    TRY(p->free_slot("utm_deflate_pull", &s));
     if (n_bytes && in != p->h_stage) memcpy(p->h_stage, in, n_bytes);
     const uint32_t n = (uint32_t)n_bytes;
     const uint32_t nseg = last ? std::max<uint32_t>(1, (n + DEF_SEG - 1) / DEF_SEG) : n / DEF_SEG;
@@ -179,36 +140,29 @@ extern "C" int utm_deflate_push(utm_deflate *p, const uint8_t *in, uint64_t n_by
     s->n = n;
     s->nseg = nseg;
     s->first = p->fresh;
-    s->pending = true;
     p->fresh = last;
-    p->next ^= 1;
-    ++p->n_pending;
+    p->queued();
     return UTM_OK;
 }
 
 extern "C" int utm_deflate_pull(utm_deflate *p, const uint8_t **out, uint64_t *out_bytes)
 {
-    DEFL(p);
+    BATCH_CTX(p, "deflate");
     if (!out || !out_bytes) return fail(UTM_EINVAL, "out or out_bytes is NULL");
     *out = nullptr;
     *out_bytes = 0;
-    if (!p->n_pending) return fail(UTM_ESTATE, "no batch to pull");
-    DefSlot *s = &p->slot[p->oldest];
-    s->pending = false;  // released on every way out
-    p->oldest ^= 1;
-    --p->n_pending;
+    DefSlot *s;
+    TRY(p->take_oldest("pull", &s));
     HIP_TRY(hipStreamSynchronize(s->stream));
     const u64 total = s->nseg ? s->h_info[0] : 0;
     HIP_TRY(hipEventRecord(s->ev[5], s->stream));
     if (total) HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, total, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipEventRecord(s->ev[6], s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    float t[5] = {};
-    HIP_TRY(hipEventElapsedTime(&t[0], s->ev[0], s->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&t[1], s->ev[1], s->ev[4]));
-    HIP_TRY(hipEventElapsedTime(&t[2], s->ev[5], s->ev[6]));
-    HIP_TRY(hipEventElapsedTime(&t[3], s->ev[2], s->ev[3]));
-    for (int i = 0; i < 4; ++i) p->ms[i] += t[i];
+    TRY(add_elapsed(&p->ms[0], s->ev[0], s->ev[1]));
+    TRY(add_elapsed(&p->ms[1], s->ev[1], s->ev[4]));
+    TRY(add_elapsed(&p->ms[2], s->ev[5], s->ev[6]));
+    TRY(add_elapsed(&p->ms[3], s->ev[2], s->ev[3]));
     if (s->first) p->a = 1, p->b = 0;
     for (uint32_t g = 0; g < s->nseg; ++g)
         def_adler_add(&p->a, &p->b, std::min<u64>(DEF_SEG, s->n - (u64)g * DEF_SEG), s->h_info[1 + 2 * g], s->h_info[2 + 2 * g]);

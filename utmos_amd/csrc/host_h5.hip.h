@@ -2,51 +2,33 @@
 // column) are decoded and packed on the device; the caller gets packbits rows, float32 AF per row and a status word
 // per chunk.
 //
-// One pinned staging buffer and two slots, each with its own stream, device buffers and pinned results:
+// One pinned staging buffer and two slots (host_batch.hip.h), each with its own device buffers and pinned results:
 // utm_h5_decode returns once its batch has reached the device and the kernels are queued, so the caller reads the next
 // batch from the file into the staging while the GPU decodes; utm_h5_fetch collects the oldest batch.
 #pragma once
 
-struct H5Slot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {};  // H2D (0-1), decode (1-2), pack (2-3), D2H (3-4)
-    uint8_t *d_in = nullptr, *d_dec = nullptr, *d_rows = nullptr, *h_rows = nullptr;
-    float *d_af = nullptr, *h_af = nullptr;
-    uint32_t *d_status = nullptr, *h_status = nullptr;
-    LzfChunk *d_chunks = nullptr, *h_chunks = nullptr;
+struct H5Slot : BatchSlot<5> {  // events around: H2D (0-1), decode (1-2), pack (2-3), D2H (3-4)
+    Scratch<uint8_t> d_in, d_dec, d_rows;
+    Pinned<uint8_t> h_rows;
+    Scratch<float> d_af;
+    Pinned<float> h_af;
+    Scratch<uint32_t> d_status;
+    Pinned<uint32_t> h_status;
+    Scratch<LzfChunk> d_chunks;
+    Pinned<LzfChunk> h_chunks;
     uint32_t n_chunks = 0;
     u64 n_rows = 0;
-    bool pending = false;
 };
 
-struct utm_h5 {
+struct utm_h5 : SlotPair<H5Slot> {
     int device = 0;
     u64 stage_cap = 0;
     uint32_t max_chunks = 0, chunk_rows = 0, n_cols = 0, itemsize = 0;
     u64 chunk_bytes = 0, dec_stride = 0, row_bytes = 0;
-    uint8_t *h_stage = nullptr;
-    H5Slot slot[2];
-    int next = 0, oldest = 0, n_pending = 0;
+    Pinned<uint8_t> h_stage;
     double ms[4] = {0, 0, 0, 0};  // H2D, decode, pack, D2H
+    ~utm_h5() { idle(device); }
 };
-
-static void h5_slot_free(H5Slot *s)
-{
-    void *host[] = {s->h_rows, s->h_af, s->h_status, s->h_chunks};
-    for (void *h : host)
-        if (h) (void)hipHostFree(h);
-    void *dev[] = {s->d_in, s->d_dec, s->d_rows, s->d_af, s->d_status, s->d_chunks};
-    for (void *d : dev)
-        if (d) (void)hipFree(d);
-    for (hipEvent_t e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    *s = H5Slot();
-}
-
-#define H5CTX(p)                                      \
-    if (!(p)) return fail(UTM_EINVAL, "h5 is NULL"); \
-    HIP_TRY(hipSetDevice((p)->device))
 
 extern "C" int utm_h5_create(int device, uint64_t stage_bytes, uint32_t max_chunks, uint32_t chunk_rows,
                              uint32_t n_cols, uint32_t itemsize, utm_h5 **out)
@@ -61,11 +43,8 @@ extern "C" int utm_h5_create(int device, uint64_t stage_bytes, uint32_t max_chun
     const u64 chunk_bytes = (u64)chunk_rows * n_cols * itemsize;
     if (chunk_bytes > UTM_H5_MAX_CHUNK_BYTES)
         return fail(UTM_EINVAL, "a chunk of %llu bytes (at most 2^31 - 2^16)", (unsigned long long)chunk_bytes);
-    int n = 0;
-    HIP_TRY(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) return fail(UTM_EINVAL, "device %d of %d", device, n);
-    HIP_TRY(hipSetDevice(device));
-    utm_h5 *p = new utm_h5();
+    TRY(open_device(device));
+    std::unique_ptr<utm_h5> p(new utm_h5());
     p->device = device;
     p->stage_cap = stage_bytes;
     p->max_chunks = max_chunks;
@@ -76,42 +55,26 @@ extern "C" int utm_h5_create(int device, uint64_t stage_bytes, uint32_t max_chun
     p->dec_stride = (chunk_bytes + 15) & ~(u64)15;
     p->row_bytes = (n_cols + 7) / 8;
     const u64 nc = max_chunks, rows = nc * chunk_rows;
-    hipError_t e = hipHostMalloc((void **)&p->h_stage, stage_bytes, hipHostMallocDefault);
+    TRY(p->h_stage.reserve(stage_bytes));
     for (H5Slot &s : p->slot) {
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-        for (hipEvent_t &ev : s.ev)
-            if (e == hipSuccess) e = hipEventCreate(&ev);
-        if (e == hipSuccess) e = hipMalloc(&s.d_in, stage_bytes + LZF_WIN);  // the decoder's window may read past the batch
-        if (e == hipSuccess) e = hipMalloc(&s.d_dec, nc * p->dec_stride);
-        if (e == hipSuccess) e = hipMalloc(&s.d_rows, rows * p->row_bytes);
-        if (e == hipSuccess) e = hipMalloc(&s.d_af, rows * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&s.d_status, nc * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&s.d_chunks, nc * sizeof(LzfChunk));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_rows, rows * p->row_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_af, rows * sizeof(float), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_status, nc * sizeof(uint32_t), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_chunks, nc * sizeof(LzfChunk), hipHostMallocDefault);
+        TRY(s.open());
+        TRY(s.d_in.reserve(stage_bytes + LZF_WIN));  // the decoder's window may read past the batch
+        TRY(s.d_dec.reserve(nc * p->dec_stride));
+        TRY(s.d_rows.reserve(rows * p->row_bytes));
+        TRY(s.d_af.reserve(rows));
+        TRY(s.d_status.reserve(nc));
+        TRY(s.d_chunks.reserve(nc));
+        TRY(s.h_rows.reserve(rows * p->row_bytes));
+        TRY(s.h_af.reserve(rows));
+        TRY(s.h_status.reserve(nc));
+        TRY(s.h_chunks.reserve(nc));
     }
-    if (e != hipSuccess) {
-        const int rc = fail(e == hipErrorOutOfMemory ? UTM_ENOMEM : UTM_EHIP, "utm_h5_create: %s", hipGetErrorString(e));
-        for (H5Slot &s : p->slot) h5_slot_free(&s);
-        if (p->h_stage) (void)hipHostFree(p->h_stage);
-        delete p;
-        return rc;
-    }
-    *out = p;
+    *out = p.release();
     return UTM_OK;
 }
 
 extern "C" int utm_h5_destroy(utm_h5 *p)
 {
-    if (!p) return UTM_OK;
-    (void)hipSetDevice(p->device);
-    for (H5Slot &s : p->slot) {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        h5_slot_free(&s);
-    }
-    if (p->h_stage) (void)hipHostFree(p->h_stage);
     delete p;
     return UTM_OK;
 }
@@ -127,14 +90,14 @@ extern "C" int utm_h5_staging(utm_h5 *p, uint8_t **buf, uint64_t *cap)
 extern "C" int utm_h5_decode(utm_h5 *p, const uint8_t *in, uint64_t n_bytes, const uint64_t *offsets,
                              const uint64_t *sizes, const uint32_t *masks, const uint32_t *rows, uint32_t n_chunks)
 {
-    H5CTX(p);
+    BATCH_CTX(p, "h5");
     if (n_chunks == 0 || n_chunks > p->max_chunks) return fail(UTM_EINVAL, "n_chunks %u not in [1, %u]", n_chunks, p->max_chunks);
     if (!offsets || !sizes || !masks || !rows) return fail(UTM_EINVAL, "offsets, sizes, masks or rows is NULL");
     if (n_bytes && !in) return fail(UTM_EINVAL, "in is NULL");
     if (n_bytes > p->stage_cap)
         return fail(UTM_EINVAL, "a batch of %llu bytes (the context takes %llu)", (unsigned long long)n_bytes, (unsigned long long)p->stage_cap);
-    H5Slot *s = &p->slot[p->next];
-    if (s->pending) return fail(UTM_ESTATE, "both slots hold a batch: utm_h5_fetch first");
+    H5Slot *s;
+    TRY(p->free_slot("utm_h5_fetch", &s));
     u64 total = 0;
     for (uint32_t i = 0; i < n_chunks; ++i) {
         if (offsets[i] > n_bytes || sizes[i] > n_bytes - offsets[i])
@@ -164,26 +127,20 @@ extern "C" int utm_h5_decode(utm_h5 *p, const uint8_t *in, uint64_t n_bytes, con
     HIP_TRY(hipEventSynchronize(s->ev[1]));  // the staging may be filled again
     s->n_chunks = n_chunks;
     s->n_rows = total;
-    s->pending = true;
-    p->next ^= 1;
-    ++p->n_pending;
+    p->queued();
     return UTM_OK;
 }
 
 extern "C" int utm_h5_fetch(utm_h5 *p, uint8_t *rows, float *af, uint32_t *status)
 {
-    H5CTX(p);
-    if (!p->n_pending) return fail(UTM_ESTATE, "no batch to fetch");
-    H5Slot *s = &p->slot[p->oldest];
-    if (!status || (s->n_rows && !rows) || (s->n_rows && p->itemsize == 4 && !af))
+    BATCH_CTX(p, "h5");
+    const H5Slot *o = p->peek_oldest();
+    if (o && (!status || (o->n_rows && !rows) || (o->n_rows && p->itemsize == 4 && !af)))
         return fail(UTM_EINVAL, "status, rows or af is NULL");
-    s->pending = false;  // released on every way out from here
-    p->oldest ^= 1;
-    --p->n_pending;
+    H5Slot *s;
+    TRY(p->take_oldest("fetch", &s));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    float t[4] = {};
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&t[i], s->ev[i], s->ev[i + 1]));
-    for (int i = 0; i < 4; ++i) p->ms[i] += t[i];
+    for (int i = 0; i < 4; ++i) TRY(add_elapsed(&p->ms[i], s->ev[i], s->ev[i + 1]));
     memcpy(status, s->h_status, s->n_chunks * sizeof(uint32_t));
     if (s->n_rows) memcpy(rows, s->h_rows, s->n_rows * p->row_bytes);
     if (s->n_rows && p->itemsize == 4) memcpy(af, s->h_af, s->n_rows * sizeof(float));

@@ -549,15 +549,47 @@ static hipError_t copy_sync(utm_ctx *c, void *dst, const void *src, size_t bytes
     return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
-// A device allocation that lives for one call: released on every way out, error returns included.
+// A device allocation owned by its holder (one call, or a context's slot): released on every way out, error returns
+// included.
 template <typename T>
 struct Scratch {
     T *p = nullptr;
+    u64 cap = 0;  // elements (reserve)
     Scratch() = default;
     Scratch(const Scratch &) = delete;
     Scratch &operator=(const Scratch &) = delete;
     ~Scratch() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
+    // Room for at least `count` elements (`floor` of them when it has to grow and that is more); drops the contents.
+    int reserve(u64 count, u64 floor = 0)
+    {
+        if (cap >= count) return UTM_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc(&p, std::max(count, floor) * sizeof(T)));
+        cap = std::max(count, floor);
+        return UTM_OK;
+    }
+    // Room for at least `count` elements, growing by half at least; keeps the first `keep` bytes, copied once `stream`
+    // is done with the old buffer.
+    int grow(u64 count, u64 keep, hipStream_t stream)
+    {
+        if (cap >= count) return UTM_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        const u64 n = std::max(count, cap + cap / 2);
+        T *q = nullptr;
+        HIP_TRY(hipMalloc(&q, n * sizeof(T)));
+        const hipError_t e = keep ? hipMemcpy(q, p, keep, hipMemcpyDeviceToDevice) : hipSuccess;
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return fail(UTM_EHIP, "keeping %llu bytes: %s", (unsigned long long)keep, hipGetErrorString(e));
+        }
+        if (p) (void)hipFree(p);
+        p = q;
+        cap = n;
+        return UTM_OK;
+    }
     operator T *() const { return p; }
 };
 
@@ -577,6 +609,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_reset.hip.h"
 #include "host_loop.hip.h"
 #include "host_shard.hip.h"
+#include "host_batch.hip.h"
 #include "host_vcf.hip.h"
 #include "host_deflate.hip.h"
 #include "host_h5.hip.h"

@@ -277,15 +277,11 @@ class GpuVcfReader:
             if len(samples) == 0:
                 return self._no_samples(path, src, samples, carry)
             h = self._context(len(samples))
-            ms0 = (ctypes.c_double * 3)()
-            nat.check(lib.utm_vcf_timing(h, ms0))
             width = (len(samples) + 7) // 8
-            pending, parts, line_base, eof = deque(), [], 0, False
-            failure = None
-            try:
+
+            def batches(carry):
+                eof = False
                 while True:
-                    if len(pending) == 2:
-                        parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
                     ptr, cap = ctypes.c_void_p(), ctypes.c_uint64()
                     nat.check(lib.utm_vcf_staging(h, max(self.batch_bytes, len(carry) + 1), ctypes.byref(ptr), ctypes.byref(cap)))
                     arr = np.ctypeslib.as_array((ctypes.c_uint8 * cap.value).from_address(ptr.value))
@@ -306,32 +302,19 @@ class GpuVcfReader:
                         # one record longer than the batch: grow the staging (it keeps its contents) and read on
                         nat.check(lib.utm_vcf_staging(h, 2 * len(arr), ctypes.byref(ptr), ctypes.byref(cap)))
                         arr = np.ctypeslib.as_array((ctypes.c_uint8 * cap.value).from_address(ptr.value))
-                    fill_s += time.perf_counter() - tf
+                    fill = time.perf_counter() - tf
                     if cut < 0:
-                        break
+                        return
                     carry = arr[cut + 1:n].tobytes()
                     n_rec = ctypes.c_uint64()
                     nat.check(lib.utm_vcf_parse(h, ptr, cut + 1, ctypes.byref(n_rec)))
-                    pending.append((n_rec.value, line_base))
-                    line_base += n_rec.value
+                    yield n_rec.value, fill
                     if eof and not carry:
-                        break
-                while pending:
-                    parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
-            except Exception as err:
-                failure = err
-            finally:
-                while pending:                 # drain the other slot: the context stays usable after a failure
-                    pending.popleft()
-                    lib.utm_vcf_fetch(h, None, None, None, None, None)
-            if failure is not None:
-                raise failure
-            ms1 = (ctypes.c_double * 3)()
-            nat.check(lib.utm_vcf_timing(h, ms1))
+                        return
+
+            parts = self._pipeline(path, h, width, n_head, batches(carry), t0)
         finally:
             src.close()
-        self.timing = {"fill_s": fill_s, "h2d_ms": ms1[0] - ms0[0], "kernel_ms": ms1[1] - ms0[1],
-                       "d2h_ms": ms1[2] - ms0[2], "inflate_ms": 0.0, "total_s": time.perf_counter() - t0}
         return self._assemble(parts, samples, width)
 
     def _read_bgzf(self, path, t0):
@@ -349,20 +332,14 @@ class GpuVcfReader:
             if len(samples) == 0:
                 return self._no_samples(path, hs, samples, prefix)
             h = self._context(len(samples))
-            ms0, inf0 = (ctypes.c_double * 3)(), ctypes.c_double()
-            nat.check(lib.utm_vcf_timing(h, ms0))
-            nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf0)))
             width = (len(samples) + 7) // 8
             table = np.array(members, dtype=np.int64).reshape(-1, 3)
             off, size, isize = table[:, 0], table[:, 1], table[:, 2]
             ends = np.cumsum(isize)
-            pending, parts, line_base, j, fill_s = deque(), [], 0, hs.next, 0.0
-            flags, failure = BGZF_FIRST, None
-            pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
-            try:
+
+            def batches(j, pre):
+                flags = BGZF_FIRST
                 while True:
-                    if len(pending) == 2:
-                        parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
                     k = j
                     if j < len(members):   # whole members, their text summed up to batch_bytes (at least one)
                         base = ends[j - 1] if j else 0
@@ -382,7 +359,7 @@ class GpuVcfReader:
                                 raise ValueError(f"{path}: truncated")
                             got += n
                     mem = np.ascontiguousarray(np.stack([size[j:k], isize[j:k]], axis=1), dtype=np.uint32)
-                    fill_s += time.perf_counter() - tf
+                    fill = time.perf_counter() - tf
                     n_rec, carry = ctypes.c_uint64(), ctypes.c_uint64()
                     rc = lib.utm_vcf_parse_bgzf(h, pre.ctypes.data if pre is not None else None,
                                                 len(pre) if pre is not None else 0, ptr, packed, mem.ctypes.data,
@@ -395,28 +372,44 @@ class GpuVcfReader:
                             msg = f"BGZF member at byte {int(off[j + int(m.group(1))])}: {m.group(2)}"
                         raise ValueError(f"{path}: {msg}")
                     nat.check(rc)
-                    pending.append((n_rec.value, line_base))
-                    line_base += n_rec.value
+                    yield n_rec.value, fill
                     flags, pre, j = 0, None, k
                     if last:
-                        break
-                while pending:
+                        return
+
+            pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
+            parts = self._pipeline(path, h, width, n_head, batches(hs.next, pre), t0)
+        return self._assemble(parts, samples, width)
+
+    def _pipeline(self, path, h, width, n_head, batches, t0):
+        """Runs the batches through the context's two slots -> the fetched parts, and sets self.timing.  `batches`
+        stages and queues one batch per step and yields (its records, seconds spent filling its staging); it is
+        resumed only once a slot is free for the next batch."""
+        lib = nat.lib()
+        ms0, inf0 = (ctypes.c_double * 3)(), ctypes.c_double()
+        nat.check(lib.utm_vcf_timing(h, ms0))
+        nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf0)))
+        pending, parts, line_base, fill_s = deque(), [], 0, 0.0
+        try:
+            for n_rec, fill in batches:
+                pending.append((n_rec, line_base))
+                line_base += n_rec
+                fill_s += fill
+                if len(pending) == 2:
                     parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
-            except Exception as err:
-                failure = err
-            finally:
-                while pending:                 # drain the other slot: the context stays usable after a failure
-                    pending.popleft()
-                    lib.utm_vcf_fetch(h, None, None, None, None, None)
-            if failure is not None:
-                raise failure
-            ms1, inf1 = (ctypes.c_double * 3)(), ctypes.c_double()
-            nat.check(lib.utm_vcf_timing(h, ms1))
-            nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf1)))
+            while pending:
+                parts.append(self._fetch(path, h, width, n_head, *pending.popleft()))
+        finally:
+            while pending:                 # drain the other slot: the context stays usable after a failure
+                pending.popleft()
+                lib.utm_vcf_fetch(h, None, None, None, None, None)
+        ms1, inf1 = (ctypes.c_double * 3)(), ctypes.c_double()
+        nat.check(lib.utm_vcf_timing(h, ms1))
+        nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf1)))
         self.timing = {"fill_s": fill_s, "h2d_ms": ms1[0] - ms0[0], "kernel_ms": ms1[1] - ms0[1],
                        "d2h_ms": ms1[2] - ms0[2], "inflate_ms": inf1.value - inf0.value,
                        "total_s": time.perf_counter() - t0}
-        return self._assemble(parts, samples, width)
+        return parts
 
     def _fetch(self, path, h, width, n_head, n_rec, line_base):
         rows = np.empty((n_rec, width), dtype=np.uint8)
