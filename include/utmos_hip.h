@@ -422,6 +422,38 @@ int utm_h5_timing(utm_h5 *h5, double *ms);
  * exactly n_out bytes, else a UTM_LZF_E_* code (out is then partly written).  Needs no GPU. */
 int utm_lzf_decode_host(const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t n_out, uint32_t *status);
 
+/* ---- HDF5 store chunks, written (no utm_ctx) ---------------------------------------------------- */
+/* The writer side: packbits rows -> the stored chunks of the `data` dataset as h5py writes them (chunk_rows x n_cols
+ * cells of itemsize bytes: 1 = h5py's bool, 4 = float32 GT * AF), LZF-compressed with the parse of h5py's filter, or
+ * raw (filter mask bit 0) where the compressed chunk would not fit in the chunk's own size (csrc/lzf_enc.hip.h).
+ * utmos_amd/h5write.py writes the file around them.  Two batch slots, each with its own stream. */
+#define UTM_H5W_MAX_BATCH_BYTES 4294901760ull /* 2^32 - 2^16 cell bytes per batch (max_chunks x chunk bytes) */
+typedef struct utm_h5w utm_h5w;
+int utm_h5w_create(int device, uint32_t chunk_rows, uint32_t n_cols, uint32_t itemsize, uint32_t max_chunks,
+                   utm_h5w **out);
+int utm_h5w_destroy(utm_h5w *h5w);
+/* The pinned staging buffer (*cap = max_chunks x chunk_rows x ceil(n_cols / 8) bytes): a caller may fill it with
+ * packbits rows and pass it to utm_h5w_encode (no copy). */
+int utm_h5w_staging(utm_h5w *h5w, uint8_t **buf, uint64_t *cap);
+/* Queue one batch: rows[n_rows * ceil(n_cols / 8)] in numpy.packbits order (the staging or any host memory), for
+ * itemsize 4 af[n_rows] (float32; the cells are float32(GT) * af).  1 <= n_rows <= max_chunks x chunk_rows; the batch
+ * is ceil(n_rows / chunk_rows) chunks, the last one zero-padded to full size unless n_rows fills it.  Returns once the
+ * rows are on the device and the kernels are queued.  At most two batches wait for utm_h5w_fetch.  A bad argument
+ * changes nothing. */
+int utm_h5w_encode(utm_h5w *h5w, const uint8_t *rows, const float *af, uint64_t n_rows);
+/* Wait for the oldest batch: *out = its chunks' stored bytes back to back in pinned memory (valid until the next
+ * utm_h5w_fetch), *out_bytes = their count, *n_chunks = the batch's chunks, sizes[*n_chunks] their stored bytes and
+ * masks[*n_chunks] their HDF5 filter masks (0: LZF, 1: raw).  sizes and masks take max_chunks entries. */
+int utm_h5w_fetch(utm_h5w *h5w, const uint8_t **out, uint64_t *out_bytes, uint32_t *sizes, uint32_t *masks,
+                  uint32_t *n_chunks);
+/* HIP-event time summed over the fetched batches: ms[0] host-to-device, ms[1] cells, ms[2] encode (scan and gather
+ * included), ms[3] device-to-host. */
+int utm_h5w_timing(utm_h5w *h5w, double *ms);
+/* The device's LZF encoder built for the CPU (liblzf's full hash table; the same bytes): in[0, n_in) -> out, at most
+ * out_cap bytes.  *out_bytes = the compressed size, or 0 when it would not fit in out_cap (h5py's filter runs with
+ * out_cap = n_in and stores such a chunk raw).  Needs no GPU. */
+int utm_lzf_encode_host(const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,12 @@ host path (utm_lzf_decode_host on up to 16 threads, then numpy packing).  The st
 from a few hundred distinct compressed chunks, so that writing it stays fast.  Prints one JSON line: seconds of both
 paths, the HIP-event split of the GPU path (h2d / decode / pack / d2h), and whether the outputs are equal.
 
-    python tools/h5_bench.py [--rows 2000000] [--samples 2504] [--kind bool|float32] [--distinct 300]
+--write measures the other direction, writing such a store from packed rows: the GPU writer (h5write.py with utm_h5w_*,
+end to end and split by HIP events: h2d / cells / encode / d2h) against the cells built by numpy and LZF-encoded by
+utm_lzf_encode_host on --threads host threads and on one thread (as liblzf runs inside h5py).  The file is not
+written by the host paths; every path's stored chunks are compared.
+
+    python tools/h5_bench.py [--rows 2000000] [--samples 2504] [--kind bool|float32] [--distinct 300] [--write]
 """
 import argparse
 import json
@@ -20,6 +25,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import h5_gen  # noqa: E402
 from utmos_amd.h5store import ChunkDecoder, H5Store, lzf_decode, pack_rows  # noqa: E402
+from utmos_amd.h5write import H5Writer, data_chunk_rows, store_chunk  # noqa: E402
 
 
 def write(path, n_rows, n_samples, kind, distinct, seed=1):
@@ -72,6 +78,65 @@ def host_load(path, threads=16):
     return time.perf_counter() - t, rows, af
 
 
+def packed_rows(n_rows, n_samples, kind, distinct, seed=1):
+    """(packbits rows, float32 AF): n_rows rows drawn from `distinct` random blocks of 997 rows."""
+    rng = np.random.default_rng(seed)
+    blocks = [np.packbits(rng.random((997, n_samples)) < rng.random() * 0.1 * rng.random((997, 1)) ** 2, axis=1)
+              for _ in range(distinct)]
+    order = rng.integers(0, distinct, (n_rows + 996) // 997)
+    rows = np.concatenate([blocks[b] for b in order])[:n_rows]
+    af = (rng.integers(1, 2 * n_samples, n_rows) / (2 * n_samples)).astype(np.float32)
+    return rows, af
+
+
+def host_encode(rows, af, n_samples, with_af, threads):
+    chunk_rows = data_chunk_rows(n_samples)
+    t = time.perf_counter()
+
+    def one(lo):
+        gt = np.unpackbits(rows[lo:lo + chunk_rows], axis=1, count=n_samples)
+        full = np.zeros((chunk_rows, n_samples), np.float32 if with_af else bool)
+        full[:len(gt)] = gt.astype(np.float32) * af[lo:lo + chunk_rows, None] if with_af else gt
+        return store_chunk(full.tobytes())
+
+    with ThreadPoolExecutor(threads) as pool:
+        chunks = list(pool.map(one, range(0, len(rows), chunk_rows)))
+    return time.perf_counter() - t, chunks
+
+
+def bench_write(args, tmp):
+    rows, af = packed_rows(args.rows, args.samples, args.kind, args.distinct)
+    with_af = args.kind == "float32"
+    names = [f"S{k:06d}" for k in range(args.samples)]
+    var_count = np.zeros(args.samples, np.int64)
+    path = os.path.join(tmp, "w.hdf5")
+    result = {}
+    for attempt in range(2):                                  # the first one warms up the library and the device
+        t = time.perf_counter()
+        with H5Writer(path, names, with_af, "gpu") as w:
+            for lo in range(0, len(rows), 1 << 18):
+                w.add_rows(rows[lo:lo + (1 << 18)], af[lo:lo + (1 << 18)])
+            split = w.enc.timing()
+            w.finish(var_count)
+        result = {"gpu_s": round(time.perf_counter() - t, 3), "gpu_ms": {k: round(v, 1) for k, v in split.items()}}
+    store = H5Store(path)
+    with open(path, "rb") as fh:
+        stored = []
+        for _row, offset, size, mask in store.data.chunks:
+            fh.seek(offset)
+            stored.append((fh.read(size), mask))
+    host_s, host = host_encode(rows, af, args.samples, with_af, args.threads)
+    one_s, one = host_encode(rows, af, args.samples, with_af, 1)
+    print(json.dumps({"mode": "write", "rows": args.rows, "samples": args.samples, "kind": args.kind,
+                      "chunks": len(stored), "raw_chunks": sum(m for _b, m in stored),
+                      "cell_bytes": args.rows * args.samples * (4 if with_af else 1),
+                      "stored_bytes": sum(len(b) for b, _m in stored), "file_bytes": os.path.getsize(path), **result,
+                      "host_s": round(host_s, 3), "host_threads": args.threads, "host1_s": round(one_s, 3),
+                      "speedup_vs_threads": round(host_s / result["gpu_s"], 2),
+                      "speedup_vs_one": round(one_s / result["gpu_s"], 2),
+                      "equal": stored == host == one}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2_000_000)
@@ -80,7 +145,12 @@ def main():
     ap.add_argument("--distinct", type=int, default=300)
     ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
     ap.add_argument("--dir", default=None)
+    ap.add_argument("--write", action="store_true", help="measure writing a store instead of loading one")
     args = ap.parse_args()
+    if args.write:
+        with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
+            bench_write(args, tmp)
+        return
     with tempfile.TemporaryDirectory(dir=args.dir) as tmp:
         path = os.path.join(tmp, "bench.hdf5")
         t = time.perf_counter()

@@ -115,6 +115,13 @@ PROTOTYPES = {
     "utm_h5_fetch": [_P, _P, _P, _P],
     "utm_h5_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_lzf_decode_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U32)],
+    "utm_h5w_create": [ctypes.c_int, _U32, _U32, _U32, _U32, ctypes.POINTER(_P)],
+    "utm_h5w_destroy": [_P],
+    "utm_h5w_staging": [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64)],
+    "utm_h5w_encode": [_P, _P, _P, _U64],
+    "utm_h5w_fetch": [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64), _P, _P, ctypes.POINTER(_U32)],
+    "utm_h5w_timing": [_P, ctypes.POINTER(ctypes.c_double)],
+    "utm_lzf_encode_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U64)],
 }
 
 _lib = None

@@ -15,3 +15,4 @@
 #include "inflate.hip.h"
 #include "deflate.hip.h"
 #include "lzf.hip.h"
+#include "lzf_enc.hip.h"

@@ -29,7 +29,7 @@ MAXMEM = 2  # GB one HBM chunk of packed columns may take; 0 = smallest chunks (
 
 HEADER = "sample\tvar_count\tnew_count\ttot_captured\tpct_captured\n"
 
-H5_SUFFIX = ".hdf5"                      # the reference's --lowmem store, read here (h5store.py), never written
+H5_SUFFIX = ".hdf5"                      # the reference's --lowmem store: read (h5store.py) and written (h5write.py)
 
 SELECTABLE, USED, EXCLUDED = 1, 0, 2      # sample_mask values (select.py:168: "1 = can use, 0 = mask, 2 = exclude")
 
@@ -225,7 +225,9 @@ class _ChunkBuilder:
         self.rows, self.af = [], []
         chunk = self.matrix.add_chunk(len(rows))
         self.matrix.upload_rows_packed(chunk, rows)          # bit transpose to columns happens on the GPU
-        if self.writer is not None:
+        if self.writer is not None and hasattr(self.writer, "add_rows"):      # hdf5: the packed rows themselves
+            self.writer.add_rows(rows, af.astype(np.float32) if self.calc_af else None)
+        elif self.writer is not None:
             self.writer.add_chunk(len(rows), self.matrix.download_columns(chunk), af.astype(np.float32) if self.calc_af else None)
         self.chunk_af.append(af)
 
@@ -289,7 +291,7 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
     """Load and concatenate the inputs into one HBM-resident matrix -> {"samples", "data", "var_count", "has_af"}.
 
     lowmem == 1: in_files[0] is an existing packed store.  lowmem == path: the store is (re)created there while
-    loading; like the reference's hdf5 it keeps AF as float32, so `--lowmem` + `--af` scores with float32 AF values
+    loading (a .hdf5 path: the reference's own store, its chunks LZF-encoded on the GPU, h5write.py); like the reference's hdf5 it keeps AF as float32, so `--lowmem` + `--af` scores with float32 AF values
     (answer_key/select_af_h5.txt) and the plain path with float64 (select_af.txt).  `buffer` = variants per chunk
     when chunking is forced (--maxmem 0).
     """
@@ -308,7 +310,10 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
         if samples is None:
             samples = np.asarray(part["samples"]).astype("U")
             matrix = _shard_matrix(len(samples), dev, shard)
-            if lowmem is not None:
+            if lowmem is not None and lowmem.endswith(H5_SUFFIX):
+                from .h5write import H5Writer
+                writer = H5Writer(lowmem, samples, calc_af, "gpu", dev)
+            elif lowmem is not None:
                 writer = StoreWriter(lowmem, samples, calc_af)
             builder = _ChunkBuilder(matrix, writer, calc_af, lowmem is not None)
         rows = np.ascontiguousarray(part["GT"], dtype=np.uint8)
@@ -387,8 +392,8 @@ def _build_parser():
                          help="never select these samples (file or comma list; repeatable)")
     memory = parser.add_argument_group("Memory Arguments")
     memory.add_argument("--lowmem", type=str, default=None,
-                        help="packed matrix store (.utm) to write, or to read (.utm, or the reference's .hdf5) when no "
-                             "inputs are given")
+                        help="matrix store to write while loading the inputs (.utm, or the reference's .hdf5), or to "
+                             "read when no inputs are given")
     memory.add_argument("--buffer", type=int, default=32768, help="variants per HBM chunk when chunking is on [%(default)s]")
     memory.add_argument("--maxmem", type=int, default=2, help="GB one chunk may take; 0 = always chunk [%(default)s]")
     gpu = parser.add_argument_group("GPU Arguments")
@@ -409,10 +414,6 @@ def parse_args(args):
     args = _build_parser().parse_args(args)
     setup_logging(args.debug)
     stores = [name for name in args.in_files if name.endswith((STORE_SUFFIX, H5_SUFFIX))]
-    if args.in_files and (args.lowmem or "").endswith(H5_SUFFIX):
-        logging.error("hdf5 stores are read, not written, by this build: create the store with --lowmem FILE%s",
-                      STORE_SUFFIX)
-        sys.exit(1)
     if stores and len(args.in_files) > 1:
         logging.error("A matrix store cannot be combined with other input files")
         sys.exit(1)
