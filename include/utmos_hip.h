@@ -123,7 +123,7 @@ typedef struct utm_stats {
     int64_t tot_captured;    /* running total of new_count */
     int64_t score_launches;  /* scoring-kernel launches since the last utm_reset */
     double score_ms;         /* summed HIP-event time of those launches (UTM_FLAG_PROFILE_EVENTS), else 0 */
-    double loop_ms;          /* HIP-event time of the last utm_run (stream time, first launch to last) */
+    double loop_ms;          /* HIP-event time of the last utm_run or utm_apply_order (stream time, first launch to last) */
     int64_t algo_bytes;      /* algorithmic HBM bytes of the iterations since the last utm_reset */
     int32_t af_mode;         /* UTM_AF_* in effect */
     int32_t af_fixed_point;  /* AF estimate: 1 = int64 fixed point at a unit no AF value loses a bit to, 2 = coarser unit
@@ -209,6 +209,21 @@ int utm_step(utm_ctx *ctx, int64_t *idx, int64_t *new_count, double *score);
  * Outputs need k_max entries (score_out may be NULL); *n_done = rows produced. */
 int utm_run(utm_ctx *ctx, int64_t k_max, int64_t *idx_out, int64_t *new_out, double *score_out,
             int64_t *n_done);
+/* Select the given samples in the given order, without scoring anyone else: new_out[i] = variants sample
+ * global_idx[i] newly captures after the ones before it (and after whatever is covered already).  Each becomes
+ * used (state 0), leaves act[], and its columns are ORed into covered; iterations and tot_captured advance.
+ * Stops like greedy_select after the row that captures the last variant: *n_done rows are valid, and only those
+ * samples become used.  A row whose new count is 0 is still a row.  Valid after utm_reset, before or between
+ * utm_run / utm_step calls.  The following utm_run continues as if those samples had been state 0 at the reset.
+ * One streaming pass over the listed columns (k_order_curve), one launch per chunk.
+ * UTM_EINVAL, with the context untouched, for NULL arguments, an index out of range, a duplicate in the list or a
+ * sample that is already used; excluded (state 2) samples are accepted.  UTM_ESTATE on a context that holds only a
+ * shard of the samples or has an exchange set up.  n == 0 is a no-op that returns 0 rows. */
+int utm_apply_order(utm_ctx *ctx, const int64_t *global_idx, int64_t n, int64_t *new_out, int64_t *n_done);
+/* The walk of k_order_curve built for the CPU: cols[s * wp + w] of one chunk, covered[wp] (updated in place), a list
+ * of n column indices; counts[i] += what column order[i] newly covers.  Needs no GPU. */
+int utm_order_curve_host(const uint64_t *cols, uint64_t wp, uint64_t *covered, const uint32_t *order, uint64_t n,
+                         uint64_t *counts);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

@@ -68,6 +68,8 @@ PROTOTYPES = {
     "utm_reset": [_P],
     "utm_step": [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_double)],
     "utm_run": [_P, _I64, _P, _P, _P, ctypes.POINTER(_I64)],
+    "utm_apply_order": [_P, _P, _I64, _P, ctypes.POINTER(_I64)],
+    "utm_order_curve_host": [_P, _U64, _P, _P, _U64, _P],
     "utm_peek_scores": [_P, _P, _P],
     "utm_peek_estimates": [_P, _P, _P],
     "utm_get_covered": [_P, _I32, _P],

@@ -100,21 +100,19 @@ static int broadcast_column(utm_ctx *c, int owner, i64 local_col)
     return UTM_OK;
 }
 
-extern "C" int utm_reset(utm_ctx *c)
+// Everything the loop keeps about the samples' states and scores, set up for `state` (n_total entries): the device state
+// and act[], cleared accumulators / records / logs, a fresh IterState, the host mirror.  `restart` (utm_reset) also
+// rebuilds covered from the used samples and zeroes the rows, the total and the statistics; without it
+// (utm_apply_order) covered is taken as it stands and the loop goes on from `iter` rows and `tot` captured variants.
+static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart, i64 iter, i64 tot)
 {
-    CTX(c);
-    if (c->chunks.empty()) return fail(UTM_ESTATE, "no chunks");
-    read_tune(&c->tune);  // the one place a live context picks up changed environment knobs
-    c->remote_winner_test = c->tune.test_remote_winner == 1;
-    TRY(build_af_tables(c));
-    TRY(ensure_xbuf(c, std::max(c->xbuf_ranks, c->n_ranks)));
     // local state + active list
     std::vector<unsigned> act;
     i64 active_total = 0;
-    for (uint32_t s = 0; s < c->n_total; ++s) active_total += c->h_state[s] == 1;
+    for (uint32_t s = 0; s < c->n_total; ++s) active_total += state[s] == 1;
     for (uint32_t s = 0; s < c->n_local; ++s)
-        if (c->h_state[c->first + s] == 1) act.push_back(s);
-    HIP_TRY(hipMemcpyAsync(c->d_state, c->h_state.data() + c->first, c->n_local, hipMemcpyHostToDevice, c->stream));
+        if (state[c->first + s] == 1) act.push_back(s);
+    HIP_TRY(hipMemcpyAsync(c->d_state, state + c->first, c->n_local, hipMemcpyHostToDevice, c->stream));
     if (!act.empty()) HIP_TRY(hipMemcpyAsync(c->d_act, act.data(), act.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_cnt, 0, (size_t)c->n_local * 8, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_cnt_alt, 0, (size_t)c->n_local * 8, c->stream));  // (a launch that ended on an error may have left partial counts)
@@ -125,13 +123,14 @@ extern "C" int utm_reset(utm_ctx *c)
     HIP_TRY(hipMemsetAsync(c->d_arrivals, 0, 128, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_vsync, 0, sizeof(VerifySync), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_known_cnt, 0xFF, (size_t)c->n_local * 8, c->stream));  // (a run that ended on an error may have left counts behind)
-    for (auto &ch : c->chunks) HIP_TRY(hipMemsetAsync(ch.covered, 0, ch.wp * 8, c->stream));
+    for (auto &ch : c->chunks)
+        if (restart) HIP_TRY(hipMemsetAsync(ch.covered, 0, ch.wp * 8, c->stream));
     // Samples that start out used cover their variants from the first iteration (select.py:36-39) -- on every
     // shard's covered replica, whoever owns the column: local columns are OR-ed in place; a peer's column is read
     // through its mapping (P2P) or broadcast by its owner (RCCL; every shard walks the same list, so the calls
     // match); a context with neither cannot know a remote column and says so.
-    for (uint32_t g = 0; g < c->n_total; ++g) {
-        if (c->h_state[g] != 0) continue;
+    for (uint32_t g = 0; restart && g < c->n_total; ++g) {
+        if (state[g] != 0) continue;
         if (g >= c->first && g < c->first + c->n_local) {
             for (auto &ch : c->chunks)
                 hipLaunchKernelGGL(k_or_column, dim3(256), dim3(256), 0, c->stream, ch.covered, ch.cols + (u64)(g - c->first) * ch.wp, ch.wp);
@@ -162,6 +161,9 @@ extern "C" int utm_reset(utm_ctx *c)
     st.n_active = (unsigned)act.size();
     st.n_active_total = active_total;
     st.prev_local = -1;
+    st.iter = iter;
+    st.tot = tot;
+    st.done = tot >= (i64)c->n_var_total && tot > 0;  // (a fixed order captured the last variant)
     st.xseq = c->xseq_host;  // the exchange sequence keeps counting across resets (every shard resets alike)
     HIP_TRY(hipMemcpyAsync(c->d_st, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -178,32 +180,46 @@ extern "C" int utm_reset(utm_ctx *c)
                 HIP_TRY(hipMalloc(&ch.list_val, ch.wp * 8));
             }
         HIP_TRY(hipMemsetAsync(c->d_listn, 0, c->chunks.size() * 4, c->stream));
-        TRY(ensure_interleaved(c));
+        if (restart) TRY(ensure_interleaved(c));  // (the copy holds columns, not states: it outlives a fixed order)
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    if (!restart) *c->h_st = st;  // (utm_get_stats reads the total from the mirror)
     c->keep_valid = false;
     c->last_new = -1;
-    c->decr_iterations = 0;
-    c->brute_bytes = 0;
     c->decr_entries_seen = c->decr_gathers_seen = 0;
-    c->iter = 0;
-    c->captured_seen = 0;
+    c->iter = iter;
+    c->captured_seen = tot;
     c->af_all_exact = false;
-    c->defer_lo = 0;
-    c->deferred_rows = 0;
-    c->scored = 0;
+    c->defer_lo = iter;  // (rows of a fixed order carry no score to finish)
     c->active_ub = (unsigned)act.size();
-    c->finished = false;
-    c->score_launches = 0;
-    c->persist_launches = c->persist_iterations = c->persist_unresolved = 0;
-    c->af_table_passes = 0;
+    c->finished = st.done != 0;
     c->loop_unresolved = false;
     c->persist_backoff = c->persist_backoff_len = 0;
-    c->score_ms = 0;
-    c->algo_bytes = 0;
     c->ev_used = 0;
+    if (restart) {  // statistics count from a utm_reset
+        c->decr_iterations = 0;
+        c->brute_bytes = 0;
+        c->deferred_rows = 0;
+        c->scored = 0;
+        c->score_launches = 0;
+        c->persist_launches = c->persist_iterations = c->persist_unresolved = 0;
+        c->af_table_passes = 0;
+        c->score_ms = 0;
+        c->algo_bytes = 0;
+    }
     c->prepared = true;
     return UTM_OK;
+}
+
+extern "C" int utm_reset(utm_ctx *c)
+{
+    CTX(c);
+    if (c->chunks.empty()) return fail(UTM_ESTATE, "no chunks");
+    read_tune(&c->tune);  // the one place a live context picks up changed environment knobs
+    c->remote_winner_test = c->tune.test_remote_winner == 1;
+    TRY(build_af_tables(c));
+    TRY(ensure_xbuf(c, std::max(c->xbuf_ranks, c->n_ranks)));
+    return reset_loop_state(c, c->h_state.data(), /*restart=*/true, 0, 0);
 }
 
 static int ensure_prepared(utm_ctx *c)

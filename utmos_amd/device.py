@@ -146,6 +146,15 @@ class DeviceMatrix:
         n = done.value
         return idx[:n].copy(), new[:n].copy(), score[:n].copy()
 
+    def apply_order(self, indices):
+        """Select the given samples (global indices) in the given order in one pass over their columns; returns the
+        new_count of each row made (fewer than listed when a row captured the last variant)."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        new = np.zeros(max(len(idx), 1), dtype=np.int64)
+        done = ctypes.c_int64(0)
+        nat.check(nat.lib().utm_apply_order(self._h, _ptr(idx), len(idx), _ptr(new), ctypes.byref(done)))
+        return new[:done.value].copy()
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)

@@ -6,6 +6,7 @@ utmos/select.py can switch over (what each one answers to is cited; the bodies a
     calculate_scores(matrix, sample_mask, sample_weights)              utmos/select.py:24-53
     greedy_select(matrix, total_variant_count, select_count, ...)      utmos/select.py:69-137
     run_selection(data, select_count, subset, exclude, weights)        utmos/select.py:147-195
+                  (+ include, mode, seed: a fixed prefix, and SVCollector's topN / random orders, utmos/select.py:140-142)
     load_files(in_files, lowmem, buffer, calc_af)                      utmos/select.py:241-321
     parse_sample_lists / parse_weights / parse_args / select_main      utmos/select.py:327-448
 
@@ -63,7 +64,8 @@ def is_memsafe(shape, with_af=False):
     return gigabytes < MAXMEM
 
 
-def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample_mask, sample_weights=None, batch=64):
+def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample_mask, sample_weights=None, batch=64,
+                  captured=0):
     """Generator of [sample, var_count, new_count, tot_captured, pct_captured], one per selected sample.
 
     matrix               device.DeviceMatrix; when it holds one shard of a multi-GPU run its exchange must be set up
@@ -73,6 +75,8 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
     vcf_samples          sample names, aligned with sample_mask
     sample_mask          1 selectable / 0 used / 2 excluded; winners are set to 0 in place, like select.py:100
     sample_weights       optional float64 per sample
+    captured             tot_captured of rows already written (the used samples of sample_mask, e.g. an --include prefix):
+                         tot_captured / pct_captured go on from there
 
     The loop itself runs on the device, `batch` iterations per call; it ends by itself when the best score is 0
     (no row for that iteration) or right after the row that captures the last variant.
@@ -84,7 +88,6 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
     matrix.set_state(np.asarray(sample_mask))
     matrix.set_weights(sample_weights)
     matrix.reset()
-    captured = 0
     wanted = int(select_count)
     while wanted > 0:
         asked = min(batch, wanted)
@@ -101,6 +104,87 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
             else:
                 logging.warning("No selectable sample adds a variant any more: stopping early")
             return
+
+
+# ---------------------------------------------------------------------------------------------- fixed orders
+MODES = ("greedy", "topN", "random")
+
+
+def fixed_order_rows(matrix, total_variant_count, order, vcf_samples, sample_mask, captured=0):
+    """Generator of greedy_select's five-field rows for the samples of `order` (indices), taken in that order whatever
+    they score: one pass over their columns on the device (utm_apply_order), no scoring of anyone else.  The matrix is
+    reset already (states and weights set); the rows go on from `captured`.  A sample that adds nothing still gets its
+    row; the rows end after the one that captures the last variant.  Sets sample_mask[i] = USED as it goes and returns
+    the running total."""
+    n_variants = matrix.shape[0]
+    if len(order) == 0:
+        return captured
+    gains = matrix.apply_order(order)
+    for sample, gain in zip(order, gains):
+        captured += gain                        # np.int64, as in greedy_select
+        sample_mask[sample] = USED
+        yield [vcf_samples[sample], int(total_variant_count[sample]), int(gain), int(captured),
+               round(captured / n_variants, 4)]
+    if len(gains) < len(order):
+        logging.warning("Every variant is captured: stopping early")
+    return captured
+
+
+def topn_order(scores, states):
+    """SVCollector's topN: the selectable samples by score, highest first, ties to the lower index (np.argmax's first
+    maximum), cut before the first score that is <= 0.  `scores` = the scores of greedy's next iteration
+    (matrix.peek_scores()), so topN is that iteration taken over and over without rescoring."""
+    scores = np.asarray(scores, dtype=np.float64)
+    candidates = np.flatnonzero(np.asarray(states) == SELECTABLE)
+    ranked = candidates[np.argsort(-scores[candidates], kind="stable")]
+    return ranked[:int((scores[ranked] > 0).sum())]     # (descending: the positive scores come first)
+
+
+def random_order(states, seed=0):
+    """SVCollector's random: a seeded permutation of the selectable samples."""
+    candidates = np.flatnonzero(np.asarray(states) == SELECTABLE)
+    return np.random.default_rng(seed).permutation(candidates)
+
+
+def resolve_include(names, include, exclude):
+    """--include names -> sample indices in the order given, later duplicates dropped.  Exits with status 1 on a name
+    the input does not have or one that is excluded as well."""
+    position = {name: i for i, name in enumerate(names)}
+    banned = set(exclude or ())
+    order = []
+    for name in include or ():
+        if name not in position:
+            logging.error("--include: sample %s is not in the input", name)
+            sys.exit(1)
+        if name in banned:
+            logging.error("--include: sample %s is excluded as well", name)
+            sys.exit(1)
+        if position[name] not in order:
+            order.append(position[name])
+    return np.asarray(order, dtype=np.int64)
+
+
+def _ordered_selection(matrix, total_variant_count, rounds, names, states, vector, included, mode, seed):
+    """Rows of a selection that starts from a fixed prefix and / or fills up in a fixed order: the prefix (all of it),
+    then what is left of `rounds` by `mode`."""
+    n_variants = matrix.shape[0]
+    if n_variants == 0:
+        logging.warning("No informative variants: nothing to select")
+        return
+    matrix.set_state(states)
+    matrix.set_weights(vector)
+    matrix.reset()
+    captured = yield from fixed_order_rows(matrix, total_variant_count, included, names, states)
+    left = rounds - len(included)
+    if left <= 0 or captured >= n_variants:
+        return
+    if mode == "greedy":        # the prefix is used now: greedy restarts from the mask and covers it again
+        yield from greedy_select(matrix, total_variant_count, left, names, states, vector, captured=captured)
+        return
+    order = topn_order(matrix.peek_scores()[1], states) if mode == "topN" else random_order(states, seed)
+    if len(order) < left:
+        logging.warning("Only %d samples left to take in %s order", len(order), mode)
+    yield from fixed_order_rows(matrix, total_variant_count, order[:left], names, states, captured)
 
 
 # ---------------------------------------------------------------------------------------------- set-up
@@ -136,8 +220,12 @@ def weight_vector(names, weights):
     return vector
 
 
-def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=None):
-    """Prepare a selection over `data` ({"data": DeviceMatrix, "samples", "var_count"}) and return its row generator."""
+def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=None, include=None, mode="greedy", seed=0):
+    """Prepare a selection over `data` ({"data": DeviceMatrix, "samples", "var_count"}) and return its row generator.
+    include: names that come first, in that order, whatever they score (they count towards select_count); mode: how
+    the rest is chosen -- greedy, or the fixed orders topN / random (seed)."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}")
     n_variants, n_samples = data["data"].shape
     logging.info("%d samples x %d informative variants", n_samples, n_variants)
     rounds = resolve_select_count(n_samples, select_count)
@@ -150,7 +238,11 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
     vector = weight_vector(names, weights)
     if vector is not None:
         logging.info("%d sample weights given", len(weights))
-    return greedy_select(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector)
+    if not include and mode == "greedy":
+        return greedy_select(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector)
+    included = resolve_include(names, include, exclude)
+    logging.info("%d samples included first; the rest in %s order", len(included), mode)
+    return _ordered_selection(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, included, mode, seed)
 
 
 # ---------------------------------------------------------------------------------------------- ingest
@@ -390,6 +482,13 @@ def _build_parser():
                          help="only consider these samples (file or comma list; repeatable)")
     scoring.add_argument("--exclude", type=str, default=None, action="append",
                          help="never select these samples (file or comma list; repeatable)")
+    scoring.add_argument("--include", type=str, default=None, action="append",
+                         help="select these samples first, in the order given, whatever they score (file or comma "
+                              "list; repeatable); they count towards --count")
+    scoring.add_argument("--mode", choices=list(MODES), default="greedy",
+                         help="how samples are chosen: greedy re-scores after every pick; topN takes the best first-"
+                              "iteration scores in order; random takes a seeded permutation [%(default)s]")
+    scoring.add_argument("--seed", type=int, default=0, help="seed of --mode random [%(default)s]")
     memory = parser.add_argument_group("Memory Arguments")
     memory.add_argument("--lowmem", type=str, default=None,
                         help="matrix store to write while loading the inputs (.utm, or the reference's .hdf5), or to "
@@ -445,6 +544,10 @@ def select_main(cmdargs):
     global MAXMEM
     args = parse_args(cmdargs)
     MAXMEM = args.maxmem
+    ordered = bool(args.include) or args.mode != "greedy"
+    if ordered and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--include and --mode %s need the whole sample axis on one GPU: run a single process", args.mode)
+        sys.exit(1)
     missing = [path for path in args.in_files if not os.path.exists(path)]
     if missing:
         logging.error("Input %s does not exist", missing[0])
@@ -488,7 +591,9 @@ def select_main(cmdargs):
     try:
         with open(args.out, "w") as fout:
             fout.write(HEADER)
-            for row in run_selection(data, args.count, subset, exclude, weights):
+            rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
+                                 args.seed) if ordered else run_selection(data, args.count, subset, exclude, weights)
+            for row in rows:
                 logging.info("%s selected: %.1f%% of the variants captured", row[0], row[4] * 100)
                 fout.write("\t".join(str(field) for field in row) + "\n")
                 fout.flush()
