@@ -220,6 +220,8 @@ int utm_run(utm_ctx *ctx, int64_t k_max, int64_t *idx_out, int64_t *new_out, dou
  * sample that is already used; excluded (state 2) samples are accepted.  UTM_ESTATE on a context that holds only a
  * shard of the samples or has an exchange set up.  n == 0 is a no-op that returns 0 rows. */
 int utm_apply_order(utm_ctx *ctx, const int64_t *global_idx, int64_t n, int64_t *new_out, int64_t *n_done);
+/* With a depth M > 1 (utm_set_depth): one k_depth_apply launch per listed sample and chunk; new_out = the units gained,
+ * and the rows end after the one that makes tot_captured = M x variants. */
 /* The walk of k_order_curve built for the CPU: cols[s * wp + w] of one chunk, covered[wp] (updated in place), a list
  * of n column indices; counts[i] += what column order[i] newly covers.  Needs no GPU. */
 int utm_order_curve_host(const uint64_t *cols, uint64_t wp, uint64_t *covered, const uint32_t *order, uint64_t n,
@@ -232,9 +234,37 @@ int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);
  * which IS the reference's float64 sum wherever the sums are exact (float32 AF, lossless unit, below 2^53 units).
  * UTM_ESTATE otherwise.  Parity/debug aid: what the tests compare the first pass with. */
 int utm_peek_estimates(utm_ctx *ctx, int64_t *counts, double *scores);
-/* Current covered mask of a chunk (all pending updates applied), ceil(n_var/64) words. */
+/* Current covered mask of a chunk (all pending updates applied), ceil(n_var/64) words.  With a depth M > 1 this is the
+ * mask the scoring uses: the variants whose support has reached M. */
 int utm_get_covered(utm_ctx *ctx, int32_t chunk, uint64_t *out);
 int utm_get_stats(utm_ctx *ctx, utm_stats *out);
+/* ---- coverage depth (set multicover) ----------------------------------------------------------- */
+/* Every variant counts until m selected samples carry it: with support(v) = the number of used samples that carry v the
+ * loop maximises F = sum_v min(support(v), m), so a sample's count is popcount(column & ~saturated) -- the scoring kernels
+ * as they are, with `covered` = the mask of variants whose support has reached m.  m = 1 (the default) is the plain
+ * selection: nothing is allocated and no other kernel runs.  m > 1 keeps bit_length(m) bit planes per chunk (plane p =
+ * bit p of every variant's support, the word layout of covered); k_depth_apply adds the winner's column after every
+ * pick, and every iteration is a full scoring pass: the persistent loop, decremental scoring, AF delta passes and
+ * deferred AF scores are off while m > 1 (utm_stats: persist_iterations, decr_iterations and af_deferred_rows stay 0).
+ * new_count = units gained, tot_captured = F, and the loop ends after the row that makes F = m x variants or when the
+ * best score is 0.  Samples that start out used (state 0) add support at utm_reset, in index order, without counting
+ * towards tot_captured.  Rows cleared by an AF of 0 have no carriers: their support stays 0 and they are in no sum.
+ * Valid before utm_reset (implies one).  UTM_EINVAL outside 1..255; m > 1 on a context that holds a shard of the samples
+ * or has an exchange set up: UTM_ESTATE, as utm_apply_order. */
+int utm_set_depth(utm_ctx *ctx, int32_t m);
+/* *m = the depth in effect; *apply_launches = k_depth_apply launches since the last utm_reset, *apply_ms their summed
+ * HIP-event time (UTM_FLAG_PROFILE_EVENTS, else 0).  Any output may be NULL. */
+int utm_get_depth(utm_ctx *ctx, int32_t *m, int64_t *apply_launches, double *apply_ms);
+/* out[i] = the number of variants with support >= m after row first_row + i (rows of utm_run / utm_step /
+ * utm_apply_order since the last utm_reset; used samples of the reset included in the count).  UTM_ESTATE at m = 1. */
+int utm_get_at_depth(utm_ctx *ctx, int64_t first_row, int64_t n_rows, int64_t *out);
+/* Per-variant support (0..m) of a chunk, n_var bytes, decoded from the planes (m = 1: the covered bit). */
+int utm_get_support(utm_ctx *ctx, int32_t chunk, uint8_t *out);
+/* k_depth_apply's word arithmetic built for the CPU: one column col[wp] into covered[wp] and planes[p * wp + w],
+ * p < bit_length(m), updated in place (covered must be the mask support == m of the planes); *units += the units gained,
+ * *newly_saturated += the variants that reached m.  Needs no GPU. */
+int utm_depth_apply_host(const uint64_t *col, uint64_t wp, uint64_t *covered, uint64_t *planes, int32_t m, uint64_t *units,
+                         uint64_t *newly_saturated);
 /* Decremental scoring: after a full scoring pass, later iterations only subtract the
  * contribution of the variants the last winner newly covered (counts and fixed-point AF sums stay exact;
  * same rows).  Reads far fewer bytes than the brute-force loop, so it is off by default and its numbers

@@ -70,6 +70,11 @@ PROTOTYPES = {
     "utm_run": [_P, _I64, _P, _P, _P, ctypes.POINTER(_I64)],
     "utm_apply_order": [_P, _P, _I64, _P, ctypes.POINTER(_I64)],
     "utm_order_curve_host": [_P, _U64, _P, _P, _U64, _P],
+    "utm_set_depth": [_P, _I32],
+    "utm_get_depth": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_double)],
+    "utm_get_at_depth": [_P, _I64, _I64, _P],
+    "utm_get_support": [_P, _I32, _P],
+    "utm_depth_apply_host": [_P, _U64, _P, _P, _I32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
     "utm_peek_scores": [_P, _P, _P],
     "utm_peek_estimates": [_P, _P, _P],
     "utm_get_covered": [_P, _I32, _P],

@@ -224,7 +224,7 @@ static LoopShape loop_shape(utm_ctx *c, int af = 0)
     const Tune &tn = c->tune;
     // (interval form: the picker keeps every selectable sample's accumulators and record in registers -- one chunk of words)
     if (af == 2 && c->n_local > (unsigned)(UTM_LOOP_THREADS * UTM_LOOP_E)) return sh;
-    if (!tn.persistent || c->persist_off || (!af && c->af_mode != UTM_AF_NONE) || c->decr_enabled || c->chunks.size() != 1 ||
+    if (!tn.persistent || c->persist_off || c->depth > 1 || (!af && c->af_mode != UTM_AF_NONE) || c->decr_enabled || c->chunks.size() != 1 ||
         c->n_ranks != 1 || c->n_local != c->n_total || c->comm || c->p2p || c->n_local >= UTM_LOOP_MAX_LOCAL ||
         (tn.persist_max_samples > 0 && c->n_local > (unsigned)tn.persist_max_samples))
         return sh;
@@ -711,6 +711,10 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
                                                                                             : batch;
         i64 n = std::min<i64>(this_batch, k_max - enq);
         const unsigned a0 = c->active_ub;
+        // depth M > 1: covered changes by more than "the winner's column ORed in" (k_depth_apply), so every iteration is a
+        // full pass against covered as it stands -- no accumulators are carried from one iteration to the next
+        const bool deep = c->depth > 1;
+        if (deep) c->keep_valid = false;
         // Decremental batches: only when allowed, when the persistent counts are current, and when the last
         // winner newly covered few enough variants (gains shrink over a greedy run, so it stays that way).
         const bool decr = c->decr_enabled && c->keep_valid && c->last_new >= 0 && (c->af_mode == UTM_AF_NONE || c->af_fixed) &&
@@ -745,10 +749,12 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         for (i64 j = 0; j < n && !loop.ok; ++j) {
             bool picked = false;
             c->enq_iter = c->iter + j;  // (exact unless the loop ends first -- and then these launches do nothing)
+            if (deep) c->keep_valid = false;
             if (verify_only) picked = false;
             else if (decr) TRY(enqueue_score_decr(c));
             else TRY(enqueue_score(c, false, fuse_mode, &picked));
             if (!picked) TRY(enqueue_pick_and_exchange(c, decr));
+            if (deep) TRY(enqueue_depth_apply(c));  // the winner into the planes; nothing stays pending
             if (af_par && j == 0 && first_is_full) hipLaunchKernelGGL(k_count_sum, dim3(1), dim3(1024), 0, c->stream, c->d_st, c->d_act, c->d_cnt, 1);
             if (c->n_ranks == 1 && c->active_ub > 0) c->active_ub -= 1;  // exact while the loop is alive
         }
@@ -792,7 +798,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         // bytes: iterations that were actually scored in this batch (rows + a terminating empty pass); the
         // local selectable count falls from a0 to a1 over the batch's rows (by one per row on a single shard)
         const i64 rows = c->iter - before;
-        const i64 passes = std::min<i64>(n, rows + ((c->finished && c->h_st->tot < (i64)c->n_var_total && rows < n) ? 1 : 0));
+        const i64 passes = std::min<i64>(n, rows + ((c->finished && c->h_st->tot < (i64)c->n_var_total * c->depth && rows < n) ? 1 : 0));
         const unsigned a1 = c->active_ub;
         {
             // folded delta passes swap the covered pair when they are ENQUEUED; the ones a finished loop skipped wrote
@@ -803,12 +809,13 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         }
         for (i64 j = 0; j < passes; ++j) {
             const u64 drop = rows > 0 ? (u64)(a0 - a1) * (u64)std::min(j, rows) / (u64)rows : 0;
-            const int kind = !af_par ? -1 : (j == 0 && first_is_full) ? UTM_PASS_AF_FULL : UTM_PASS_AF_DELTA;
-            const i64 full = iteration_bytes(c, a0 - drop, kind);
+            const int kind = !af_par ? -1 : ((j == 0 && first_is_full) || deep) ? UTM_PASS_AF_FULL : UTM_PASS_AF_DELTA;
+            i64 full = iteration_bytes(c, a0 - drop, kind);
+            if (deep && j < rows) full += (i64)(2 * c->depth_planes + 3) * (i64)c->col_words * 8;  // k_depth_apply: column, covered and planes in and out
             c->brute_bytes += full;
             if (!decr) c->algo_bytes += full;
         }
-        if (af_par && rows > 0) {
+        if (af_par && rows > 0 && !deep) {
             // AF values the delta passes of this batch gathered = how far the selectable samples' counts fell, less
             // what left with the winners themselves (4 bytes per fixed-point table entry)
             const i64 skip = first_is_full ? 1 : 0;
@@ -847,6 +854,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         tail_deferred = defer;
         c->scored += passes;
         if (c->flags & UTM_FLAG_PROFILE_EVENTS) TRY(collect_event_times(c));
+        if (deep && (c->flags & UTM_FLAG_PROFILE_EVENTS)) TRY(collect_depth_times(c));
     }
     if (tail_deferred) TRY(defer_flush_last(c));
     HIP_TRY(hipEventRecord(c->ev_loop1, c->stream));
@@ -1017,7 +1025,8 @@ extern "C" int utm_stream_calibration(utm_ctx *c, int32_t launches, double *gbps
 extern "C" int utm_set_decremental(utm_ctx *c, int32_t on, double threshold)
 {
     CTX(c);
-    c->decr_enabled = on != 0;
+    c->decr_requested = on != 0;
+    c->decr_enabled = c->decr_requested && c->depth == 1;  // (depth M > 1 keeps the full passes: utm_set_depth)
     c->decr_threshold = threshold > 0 ? threshold : 0;
     if (!on) {  // the interleaved copy doubles the matrix: hand it back with the mode
         HIP_TRY(hipStreamSynchronize(c->stream));

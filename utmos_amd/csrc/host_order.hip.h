@@ -1,4 +1,5 @@
-// Fixed orders: utm_apply_order (one k_order_curve launch per chunk) and the CPU build of its loop.
+// Fixed orders: utm_apply_order (one k_order_curve launch per chunk; depth M > 1: one k_depth_apply per listed sample and
+// chunk) and the CPU build of its loop.
 // Part of the one translation unit utmos_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
@@ -28,7 +29,9 @@ extern "C" int utm_apply_order(utm_ctx *c, const int64_t *global_idx, int64_t n,
             order[(size_t)i] = (unsigned)g;
         }
     }
-    if (n == 0 || c->captured_seen >= (i64)c->n_var_total) return UTM_OK;  // nothing listed / nothing left to capture
+    const bool deep = c->depth > 1;  // every listed column goes through k_depth_apply, gains = units
+    const i64 f_max = (i64)c->n_var_total * c->depth;
+    if (n == 0 || c->captured_seen >= f_max) return UTM_OK;  // nothing listed / nothing left to capture
 
     Scratch<unsigned> d_order;
     Scratch<u64> d_counts;
@@ -36,12 +39,20 @@ extern "C" int utm_apply_order(utm_ctx *c, const int64_t *global_idx, int64_t n,
     HIP_TRY(d_counts.alloc((size_t)n));
     HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_counts.p, 0, (size_t)n * 8, c->stream));
+    Scratch<u64> d_sat;  // depth: variants that became saturated, per listed sample
+    if (deep) {
+        HIP_TRY(d_sat.alloc((size_t)n));
+        HIP_TRY(hipMemsetAsync(d_sat.p, 0, (size_t)n * 8, c->stream));
+    }
     HIP_TRY(hipEventRecord(c->ev_loop0, c->stream));
     TRY(flush_pending(c));  // the last winner's column may still be waiting for the next scoring launch
     const bool use_nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)n * c->col_words * 8 > ((u64)c->tune.nt_min_mb << 20);
     for (auto &ch : c->chunks) {
         const dim3 grid((unsigned)((ch.wp + UTM_ORDER_TILE_WORDS - 1) / UTM_ORDER_TILE_WORDS));
-        if (use_nt)
+        if (deep)
+            for (i64 i = 0; i < n; ++i)
+                launch_depth_apply(c, ch, ch.cols + (u64)order[(size_t)i] * ch.wp, d_counts.p + i, d_sat.p + i, false);
+        else if (use_nt)
             hipLaunchKernelGGL(k_order_curve<true>, grid, dim3(256), 0, c->stream, (const u64 *)ch.cols, ch.covered, ch.wp,
                                (const unsigned *)d_order.p, (unsigned)n, d_counts.p);
         else
@@ -54,6 +65,17 @@ extern "C" int utm_apply_order(utm_ctx *c, const int64_t *global_idx, int64_t n,
     HIP_TRY(hipEventRecord(c->ev_loop1, c->stream));
     std::vector<u64> counts((size_t)n);
     HIP_TRY(copy_sync(c, counts.data(), d_counts.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    std::vector<i64> at_depth;
+    if (deep) {
+        // the running number of saturated variants after each row (columns behind the last row found nothing to add)
+        std::vector<u64> sat((size_t)n);
+        u64 running = 0;
+        HIP_TRY(copy_sync(c, sat.data(), d_sat.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(c, &running, c->d_depth_acc + 1, 8, hipMemcpyDeviceToHost));
+        for (i64 i = 0; i < n; ++i) at_depth.push_back((i64)(running += sat[(size_t)i]));
+        HIP_TRY(copy_sync(c, c->d_depth_acc + 1, &running, 8, hipMemcpyHostToDevice));
+        if (c->flags & UTM_FLAG_PROFILE_EVENTS) TRY(collect_depth_times(c));
+    }
 
     // Rows end after the one that captures the last variant.  The columns listed behind it were ORed into a mask that was
     // complete already, so covered is what the rows alone make it; those samples keep their states.
@@ -66,17 +88,18 @@ extern "C" int utm_apply_order(utm_ctx *c, const int64_t *global_idx, int64_t n,
         state[g] = 0;
         idx.push_back((i64)g);
         rows += 1;
-        if (tot >= (i64)c->n_var_total) break;
+        if (tot >= f_max) break;
     }
     const i64 iter0 = c->iter;
     HIP_TRY(hipMemcpyAsync(c->d_res_idx + iter0, idx.data(), (size_t)rows * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_res_new + iter0, new_out, (size_t)rows * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_res_score + iter0, 0, (size_t)rows * 8, c->stream));
+    if (deep) HIP_TRY(hipMemcpyAsync(c->d_res_sat + iter0, at_depth.data(), (size_t)rows * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (idx and new_out are the caller's / this call's memory)
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev_loop0, c->ev_loop1));
     c->loop_ms = ms;  // (utm_stats.loop_ms: the pass, as for a utm_run)
-    c->algo_bytes += (i64)((u64)n + 2) * (i64)c->col_words * 8;
+    c->algo_bytes += deep ? (i64)n * (2 * c->depth_planes + 3) * (i64)c->col_words * 8 : (i64)((u64)n + 2) * (i64)c->col_words * 8;
     // Everything cached about scores goes: counts by position in act[], AF sums and records, the decremental copy's
     // bookkeeping, the persistent loop's words -- the path of utm_reset, with covered, the rows and the total kept.
     TRY(reset_loop_state(c, state.data(), /*restart=*/false, iter0 + rows, tot));

@@ -125,6 +125,7 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
     HIP_TRY(hipMemsetAsync(c->d_known_cnt, 0xFF, (size_t)c->n_local * 8, c->stream));  // (a run that ended on an error may have left counts behind)
     for (auto &ch : c->chunks)
         if (restart) HIP_TRY(hipMemsetAsync(ch.covered, 0, ch.wp * 8, c->stream));
+    if (restart) TRY(depth_prepare(c));
     // Samples that start out used cover their variants from the first iteration (select.py:36-39) -- on every
     // shard's covered replica, whoever owns the column: local columns are OR-ed in place; a peer's column is read
     // through its mapping (P2P) or broadcast by its owner (RCCL; every shard walks the same list, so the calls
@@ -132,8 +133,11 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
     for (uint32_t g = 0; restart && g < c->n_total; ++g) {
         if (state[g] != 0) continue;
         if (g >= c->first && g < c->first + c->n_local) {
-            for (auto &ch : c->chunks)
-                hipLaunchKernelGGL(k_or_column, dim3(256), dim3(256), 0, c->stream, ch.covered, ch.cols + (u64)(g - c->first) * ch.wp, ch.wp);
+            for (auto &ch : c->chunks) {
+                // depth M > 1: a used sample adds support (covered = the variants that M of them carry)
+                if (c->depth > 1) launch_depth_apply(c, ch, ch.cols + (u64)(g - c->first) * ch.wp, c->d_depth_acc, c->d_depth_acc + 1, false);
+                else hipLaunchKernelGGL(k_or_column, dim3(256), dim3(256), 0, c->stream, ch.covered, ch.cols + (u64)(g - c->first) * ch.wp, ch.wp);
+            }
             if (!c->comm || c->p2p || c->n_ranks == 1) continue;
         }
         if (c->n_local == c->n_total) continue;
@@ -163,7 +167,7 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
     st.prev_local = -1;
     st.iter = iter;
     st.tot = tot;
-    st.done = tot >= (i64)c->n_var_total && tot > 0;  // (a fixed order captured the last variant)
+    st.done = tot >= (i64)c->n_var_total * c->depth && tot > 0;  // (a fixed order captured the last variant)
     st.xseq = c->xseq_host;  // the exchange sequence keeps counting across resets (every shard resets alike)
     HIP_TRY(hipMemcpyAsync(c->d_st, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -281,7 +285,7 @@ static PickArgs pick_args(utm_ctx *c, bool decr = false)
     a.res_idx = c->d_res_idx;
     a.res_new = c->d_res_new;
     a.res_score = c->d_res_score;
-    a.n_var_total = (i64)c->n_var_total;
+    a.n_var_total = (i64)c->n_var_total * c->depth;  // F = sum of min(support, depth) ends at depth x variants
     a.first = c->first;
     a.n_local = c->n_local;
     a.n_total = c->n_total;

@@ -264,6 +264,7 @@ struct Chunk {
     unsigned *list_idx = nullptr;  // decremental scoring: words newly covered by the last winner
     u64 *list_val = nullptr;
     u64 *rows_t = nullptr;         // decremental scoring: word-interleaved copy [wp][s_t] (optional: needs the room)
+    u64 *planes = nullptr;         // coverage depth M > 1: bit_length(M) planes of wp words, plane p = bit p of every variant's support
     bool rows_t_valid = false;
     std::vector<float> h_af32;
     std::vector<double> h_af64;
@@ -332,7 +333,18 @@ struct utm_ctx {
     i64 *d_afsum_keep = nullptr;
     unsigned *d_listn = nullptr; // per chunk
     size_t listn_cap = 0;
-    bool decr_enabled = false;
+    bool decr_enabled = false;      // decremental scoring is in effect (requested, and the depth is 1)
+    bool decr_requested = false;    // ... as asked for (utm_set_decremental / UTM_FLAG_DECREMENTAL)
+    // coverage depth (utm_set_depth, depth.hip.h): a variant counts until `depth` selected samples carry it
+    int depth = 1;
+    int depth_planes = 0;           // bit_length(depth) while depth > 1
+    u64 *d_depth_acc = nullptr;     // [0] units gained, [1] saturated variants: running sums since the last utm_reset
+    DepthSync *d_depth_sync = nullptr;
+    i64 *d_res_sat = nullptr;       // per row: saturated variants after it
+    i64 depth_launches = 0;         // k_depth_apply launches since the last utm_reset
+    double depth_ms = 0.0;          // ... their summed HIP-event time (UTM_FLAG_PROFILE_EVENTS)
+    std::vector<hipEvent_t> ev_depth;
+    size_t ev_depth_used = 0;
     bool decr_interleaved = false;  // the chunks carry a word-interleaved copy: decremental iterations stream it
     double decr_threshold = 0;  // <= 0: by layout (1.0 streaming the interleaved copy, 0.2 gathering)
     bool keep_valid = false;     // the persistent counts describe the state right before the pending winner
@@ -413,7 +425,7 @@ static bool remote_reads(const utm_ctx *c) { return c->p2p && !c->replicated && 
 // shard's verified-parallel loop, exact scores wanted, buffers in place, estimates not (yet) all exact.
 static bool defer_active(const utm_ctx *c)
 {
-    return c->d_newly_log && c->af_exact_scores && c->af_mode != UTM_AF_NONE && c->af_fixed && !c->af_all_exact && !c->decr_enabled &&
+    return c->d_newly_log && c->depth == 1 && c->af_exact_scores && c->af_mode != UTM_AF_NONE && c->af_fixed && !c->af_all_exact && !c->decr_enabled &&
            c->n_ranks == 1 && c->n_local == c->n_total && !c->comm && !c->p2p;
 }
 
@@ -490,7 +502,7 @@ extern "C" int utm_ctx_create(int device, uint32_t n_samp_total, uint32_t first_
     HIP_TRY(hipMemsetAsync(c->d_vsync, 0, sizeof(VerifySync), c->stream));
     HIP_TRY(hipMalloc(&c->d_cnt_keep, (size_t)n_samp_local * 8));
     HIP_TRY(hipMalloc(&c->d_afsum_keep, (size_t)n_samp_local * 8));
-    c->decr_enabled = flags & UTM_FLAG_DECREMENTAL;
+    c->decr_enabled = c->decr_requested = flags & UTM_FLAG_DECREMENTAL;
     c->remote_winner_test = c->tune.test_remote_winner == 1;
     c->xbuf_ranks = 1;
     HIP_TRY(hipEventCreate(&c->ev_loop0));
@@ -519,7 +531,10 @@ extern "C" int utm_ctx_destroy(utm_ctx *c)
         (void)hipFree(ch.rows_t);
         (void)hipFree(ch.list_val);
         (void)hipFree(ch.mask);
+        (void)hipFree(ch.planes);
     }
+    (void)hipFree(c->d_depth_acc); (void)hipFree(c->d_depth_sync); (void)hipFree(c->d_res_sat);
+    for (auto e : c->ev_depth) (void)hipEventDestroy(e);
     (void)hipFree(c->d_cand);
     (void)hipFree(c->d_arrivals);
     (void)hipFree(c->d_vsync);
@@ -606,6 +621,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 
 #include "host_matrix.hip.h"
 #include "host_options.hip.h"
+#include "host_depth.hip.h"
 #include "host_reset.hip.h"
 #include "host_loop.hip.h"
 #include "host_order.hip.h"

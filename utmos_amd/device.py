@@ -25,6 +25,7 @@ class DeviceMatrix:
         self.p2p = False
         self.fused = False      # run() is collective over the shards (mailboxes or RCCL)
         self.fused_mailboxes = False
+        self.coverage_depth = 1
         flags = (nat.FLAG_PROFILE_EVENTS if profile_events else 0) | (nat.FLAG_AF_SEQUENTIAL if af_sequential else 0)
         code = nat.lib().utm_ctx_create(int(device), self.n_samples, self.first_sample, self.n_local, flags,
                                         ctypes.byref(self._h))
@@ -181,6 +182,30 @@ class DeviceMatrix:
     def set_decremental(self, on, threshold=0.0):
         """Allow decremental scoring for later iterations (exact; fewer bytes; reported separately)."""
         nat.check(nat.lib().utm_set_decremental(self._h, 1 if on else 0, float(threshold)))
+
+    def set_depth(self, m):
+        """Coverage depth: every variant counts until m selected samples carry it (1 = the plain selection).  Takes
+        effect with the next reset."""
+        nat.check(nat.lib().utm_set_depth(self._h, int(m)))
+        self.coverage_depth = int(m)
+
+    def depth(self):
+        """{"depth", "apply_launches", "apply_ms"}: the depth in effect and what k_depth_apply has cost since the reset."""
+        m, launches, ms = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_get_depth(self._h, ctypes.byref(m), ctypes.byref(launches), ctypes.byref(ms)))
+        return {"depth": m.value, "apply_launches": launches.value, "apply_ms": ms.value}
+
+    def at_depth(self, first_row, n_rows):
+        """Variants with support >= depth after each of the rows [first_row, first_row + n_rows) (depth > 1)."""
+        out = np.zeros(max(int(n_rows), 1), dtype=np.int64)
+        nat.check(nat.lib().utm_get_at_depth(self._h, int(first_row), int(n_rows), _ptr(out)))
+        return out[:int(n_rows)].copy()
+
+    def support(self, chunk):
+        """Per-variant support of a chunk: how many used samples carry it, saturating at the depth (uint8)."""
+        out = np.zeros(self.chunk_vars[chunk], dtype=np.uint8)
+        nat.check(nat.lib().utm_get_support(self._h, chunk, _ptr(out)))
+        return out
 
     def set_af_exact_scores(self, on):
         """AF modes: off = skip the sequential chain of an unambiguous winner (same rows; scores become estimates)."""

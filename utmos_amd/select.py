@@ -29,6 +29,8 @@ from .store import StoreReader, StoreWriter
 MAXMEM = 2  # GB one HBM chunk of packed columns may take; 0 = smallest chunks (the reference's test hook, select.py:18-19)
 
 HEADER = "sample\tvar_count\tnew_count\ttot_captured\tpct_captured\n"
+HEADER_DEPTH = HEADER[:-1] + "\tat_depth\n"   # --depth M > 1: + variants that M selected samples carry
+MAX_DEPTH = 255
 
 H5_SUFFIX = ".hdf5"                      # the reference's --lowmem store: read (h5store.py) and written (h5write.py)
 
@@ -64,8 +66,18 @@ def is_memsafe(shape, with_af=False):
     return gigabytes < MAXMEM
 
 
+def _depth_rows(matrix, rows, depth):
+    """With depth > 1 every row gets a sixth field: the variants whose support has reached the depth after it (the
+    device keeps that count per row)."""
+    if depth > 1 and rows:
+        done = matrix.stats()["iterations"]
+        for row, saturated in zip(rows, matrix.at_depth(done - len(rows), len(rows))):
+            row.append(int(saturated))
+    return rows
+
+
 def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample_mask, sample_weights=None, batch=64,
-                  captured=0):
+                  captured=0, depth=1):
     """Generator of [sample, var_count, new_count, tot_captured, pct_captured], one per selected sample.
 
     matrix               device.DeviceMatrix; when it holds one shard of a multi-GPU run its exchange must be set up
@@ -77,6 +89,9 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
     sample_weights       optional float64 per sample
     captured             tot_captured of rows already written (the used samples of sample_mask, e.g. an --include prefix):
                          tot_captured / pct_captured go on from there
+    depth                M: every variant counts until M selected samples carry it.  With M > 1 new_count is the units
+                         gained, tot_captured = F = sum of min(support, M), pct_captured = F / (M * variants), and a
+                         sixth field says how many variants have support >= M
 
     The loop itself runs on the device, `batch` iterations per call; it ends by itself when the best score is 0
     (no row for that iteration) or right after the row that captures the last variant.
@@ -87,19 +102,24 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
         return
     matrix.set_state(np.asarray(sample_mask))
     matrix.set_weights(sample_weights)
+    if depth != getattr(matrix, "coverage_depth", 1):     # (depth 1 on a matrix that never left it: nothing to say)
+        matrix.set_depth(depth)
     matrix.reset()
+    units = n_variants * depth                  # what tot_captured can reach
     wanted = int(select_count)
     while wanted > 0:
         asked = min(batch, wanted)
         winners, gains, _ = matrix.run(asked)   # up to `asked` iterations, no host round trip in between
+        rows = []
         for winner, gain in zip(winners, gains):
             captured += gain                    # stays np.int64: the ratio below is then numpy's division and rounding
             sample_mask[winner] = USED
-            yield [vcf_samples[winner], int(total_variant_count[winner]), int(gain), int(captured),
-                   round(captured / n_variants, 4)]
+            rows.append([vcf_samples[winner], int(total_variant_count[winner]), int(gain), int(captured),
+                         round(captured / units, 4)])
+        yield from _depth_rows(matrix, rows, depth)
         wanted -= len(winners)
         if len(winners) < asked:                # the device loop stopped on its own
-            if captured >= n_variants:
+            if captured >= units:
                 logging.warning("Every variant is captured: stopping early")
             else:
                 logging.warning("No selectable sample adds a variant any more: stopping early")
@@ -110,21 +130,23 @@ def greedy_select(matrix, total_variant_count, select_count, vcf_samples, sample
 MODES = ("greedy", "topN", "random")
 
 
-def fixed_order_rows(matrix, total_variant_count, order, vcf_samples, sample_mask, captured=0):
+def fixed_order_rows(matrix, total_variant_count, order, vcf_samples, sample_mask, captured=0, depth=1):
     """Generator of greedy_select's five-field rows for the samples of `order` (indices), taken in that order whatever
     they score: one pass over their columns on the device (utm_apply_order), no scoring of anyone else.  The matrix is
     reset already (states and weights set); the rows go on from `captured`.  A sample that adds nothing still gets its
     row; the rows end after the one that captures the last variant.  Sets sample_mask[i] = USED as it goes and returns
     the running total."""
-    n_variants = matrix.shape[0]
+    units = matrix.shape[0] * depth
     if len(order) == 0:
         return captured
     gains = matrix.apply_order(order)
+    rows = []
     for sample, gain in zip(order, gains):
         captured += gain                        # np.int64, as in greedy_select
         sample_mask[sample] = USED
-        yield [vcf_samples[sample], int(total_variant_count[sample]), int(gain), int(captured),
-               round(captured / n_variants, 4)]
+        rows.append([vcf_samples[sample], int(total_variant_count[sample]), int(gain), int(captured),
+                     round(captured / units, 4)])
+    yield from _depth_rows(matrix, rows, depth)
     if len(gains) < len(order):
         logging.warning("Every variant is captured: stopping early")
     return captured
@@ -164,7 +186,7 @@ def resolve_include(names, include, exclude):
     return np.asarray(order, dtype=np.int64)
 
 
-def _ordered_selection(matrix, total_variant_count, rounds, names, states, vector, included, mode, seed):
+def _ordered_selection(matrix, total_variant_count, rounds, names, states, vector, included, mode, seed, depth=1):
     """Rows of a selection that starts from a fixed prefix and / or fills up in a fixed order: the prefix (all of it),
     then what is left of `rounds` by `mode`."""
     n_variants = matrix.shape[0]
@@ -173,18 +195,20 @@ def _ordered_selection(matrix, total_variant_count, rounds, names, states, vecto
         return
     matrix.set_state(states)
     matrix.set_weights(vector)
+    if depth != getattr(matrix, "coverage_depth", 1):     # (depth 1 on a matrix that never left it: nothing to say)
+        matrix.set_depth(depth)
     matrix.reset()
-    captured = yield from fixed_order_rows(matrix, total_variant_count, included, names, states)
+    captured = yield from fixed_order_rows(matrix, total_variant_count, included, names, states, depth=depth)
     left = rounds - len(included)
-    if left <= 0 or captured >= n_variants:
+    if left <= 0 or captured >= n_variants * depth:
         return
     if mode == "greedy":        # the prefix is used now: greedy restarts from the mask and covers it again
-        yield from greedy_select(matrix, total_variant_count, left, names, states, vector, captured=captured)
+        yield from greedy_select(matrix, total_variant_count, left, names, states, vector, captured=captured, depth=depth)
         return
     order = topn_order(matrix.peek_scores()[1], states) if mode == "topN" else random_order(states, seed)
     if len(order) < left:
         logging.warning("Only %d samples left to take in %s order", len(order), mode)
-    yield from fixed_order_rows(matrix, total_variant_count, order[:left], names, states, captured)
+    yield from fixed_order_rows(matrix, total_variant_count, order[:left], names, states, captured, depth)
 
 
 # ---------------------------------------------------------------------------------------------- set-up
@@ -220,12 +244,17 @@ def weight_vector(names, weights):
     return vector
 
 
-def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=None, include=None, mode="greedy", seed=0):
+def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=None, include=None, mode="greedy", seed=0,
+                  depth=1):
     """Prepare a selection over `data` ({"data": DeviceMatrix, "samples", "var_count"}) and return its row generator.
     include: names that come first, in that order, whatever they score (they count towards select_count); mode: how
-    the rest is chosen -- greedy, or the fixed orders topN / random (seed)."""
+    the rest is chosen -- greedy, or the fixed orders topN / random (seed); depth: how many selected samples should
+    carry every variant (rows get a sixth field when it is above 1)."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}")
+    if not 1 <= int(depth) <= MAX_DEPTH:
+        raise ValueError(f"depth must be in 1..{MAX_DEPTH}")
+    depth = int(depth)
     n_variants, n_samples = data["data"].shape
     logging.info("%d samples x %d informative variants", n_samples, n_variants)
     rounds = resolve_select_count(n_samples, select_count)
@@ -239,10 +268,11 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
     if vector is not None:
         logging.info("%d sample weights given", len(weights))
     if not include and mode == "greedy":
-        return greedy_select(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector)
+        return greedy_select(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, depth=depth)
     included = resolve_include(names, include, exclude)
     logging.info("%d samples included first; the rest in %s order", len(included), mode)
-    return _ordered_selection(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, included, mode, seed)
+    return _ordered_selection(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, included, mode, seed,
+                              depth)
 
 
 # ---------------------------------------------------------------------------------------------- ingest
@@ -489,6 +519,10 @@ def _build_parser():
                          help="how samples are chosen: greedy re-scores after every pick; topN takes the best first-"
                               "iteration scores in order; random takes a seeded permutation [%(default)s]")
     scoring.add_argument("--seed", type=int, default=0, help="seed of --mode random [%(default)s]")
+    scoring.add_argument("--depth", type=int, default=1,
+                         help="every variant counts until this many selected samples carry it (1..255); above 1 "
+                              "new_count / tot_captured count units of min(support, depth) and a column at_depth is "
+                              "added [%(default)s]")
     memory = parser.add_argument_group("Memory Arguments")
     memory.add_argument("--lowmem", type=str, default=None,
                         help="matrix store to write while loading the inputs (.utm, or the reference's .hdf5), or to "
@@ -515,6 +549,9 @@ def parse_args(args):
     stores = [name for name in args.in_files if name.endswith((STORE_SUFFIX, H5_SUFFIX))]
     if stores and len(args.in_files) > 1:
         logging.error("A matrix store cannot be combined with other input files")
+        sys.exit(1)
+    if not 1 <= args.depth <= MAX_DEPTH:
+        logging.error("--depth must be between 1 and %d", MAX_DEPTH)
         sys.exit(1)
     if not args.in_files and not args.lowmem:
         logging.error("Nothing to read: give input files, or --lowmem STORE to select from an existing store")
@@ -547,6 +584,9 @@ def select_main(cmdargs):
     ordered = bool(args.include) or args.mode != "greedy"
     if ordered and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--include and --mode %s need the whole sample axis on one GPU: run a single process", args.mode)
+        sys.exit(1)
+    if args.depth > 1 and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--depth above 1 needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
     missing = [path for path in args.in_files if not os.path.exists(path)]
     if missing:
@@ -590,9 +630,12 @@ def select_main(cmdargs):
     weights = parse_weights(args.weights)
     try:
         with open(args.out, "w") as fout:
-            fout.write(HEADER)
-            rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
-                                 args.seed) if ordered else run_selection(data, args.count, subset, exclude, weights)
+            fout.write(HEADER_DEPTH if args.depth > 1 else HEADER)
+            if ordered:
+                rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
+                                     args.seed, args.depth)
+            else:
+                rows = run_selection(data, args.count, subset, exclude, weights, depth=args.depth)
             for row in rows:
                 logging.info("%s selected: %.1f%% of the variants captured", row[0], row[4] * 100)
                 fout.write("\t".join(str(field) for field in row) + "\n")
