@@ -226,6 +226,26 @@ int utm_apply_order(utm_ctx *ctx, const int64_t *global_idx, int64_t n, int64_t 
  * of n column indices; counts[i] += what column order[i] newly covers.  Needs no GPU. */
 int utm_order_curve_host(const uint64_t *cols, uint64_t wp, uint64_t *covered, const uint32_t *order, uint64_t n,
                          uint64_t *counts);
+/* ---- capture ranks ---------------------------------------------------------------------------- */
+/* For a list of samples and a depth m in 1..255: rank_out[v] = the smallest i such that m of the samples
+ * global_idx[0..i] carry variant v of the chunk, or -1 when the list never gets there (m = 1: the position of v's first
+ * carrier).  One int32 per variant answers every prefix panel of the list at once: a panel of the first k samples
+ * captures the variants with 0 <= rank < k.  rank_out takes the chunk's n_var values.  One streaming pass over the
+ * listed columns of the chunk (k_capture_rank), one launch; *pass_ms = its HIP-event time (may be NULL).
+ * Stateless: it reads the chunk's columns and nothing else, and starts from an empty mask whatever the context's states
+ * are -- covered, the depth planes, the sample states, the rows, a pending winner, utm_stats and everything the loop
+ * caches are neither read nor changed, so a utm_run before or after it is unaffected.  Valid any time after the chunk's
+ * columns are uploaded.  Used and excluded samples are accepted in the list.  Rows cleared by an AF of 0 (utm_set_af)
+ * have no carriers: -1.  n == 0: all -1.
+ * UTM_EINVAL, with rank_out untouched, for a NULL global_idx with n > 0, a NULL rank_out, a chunk or an index out of
+ * range, a duplicate in the list, or m outside 1..255.  UTM_ESTATE on a context that holds only a shard of the samples
+ * or has an exchange set up, as utm_apply_order. */
+int utm_capture_rank(utm_ctx *ctx, int32_t chunk, const int64_t *global_idx, int64_t n, int32_t m,
+                     int32_t *rank_out /* n_var of the chunk */, double *pass_ms /* may be NULL */);
+/* The walk of k_capture_rank built for the CPU: cols[s * wp + w] of one chunk holding n_var <= 64 * wp variants, a list
+ * of n column indices, a depth m in 1..255; rank_out[n_var] as above.  Needs no GPU. */
+int utm_capture_rank_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, const uint32_t *order, uint64_t n,
+                          int32_t m, int32_t *rank_out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

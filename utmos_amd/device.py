@@ -156,6 +156,17 @@ class DeviceMatrix:
         nat.check(nat.lib().utm_apply_order(self._h, _ptr(idx), len(idx), _ptr(new), ctypes.byref(done)))
         return new[:done.value].copy()
 
+    def capture_rank(self, chunk, indices, depth=1, pass_ms=False):
+        """int32 per variant of a chunk: the position in `indices` (global sample indices, in order) at which `depth` of
+        the listed samples carry the variant, -1 if that never happens.  Stateless: one pass over the listed columns,
+        nothing of the selection is read or changed.  pass_ms: return (ranks, HIP-event time of the pass) instead."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        out = np.empty(self.chunk_vars[chunk], dtype=np.int32)
+        ms = ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_capture_rank(self._h, int(chunk), _ptr(idx), len(idx), int(depth), _ptr(out),
+                                             ctypes.byref(ms) if pass_ms else None))
+        return (out, ms.value) if pass_ms else out
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)

@@ -305,8 +305,9 @@ def _shard_matrix(n_samples, dev, shard):
     return device.DeviceMatrix(n_samples, device=dev, first_sample=first, n_local=n_local)
 
 
-def load_store(path, dev=0, shard=None):
-    """Open a packed store and upload this process's columns, chunk by chunk, from a memory map."""
+def load_store(path, dev=0, shard=None, origin=False):
+    """Open a packed store and upload this process's columns, chunk by chunk, from a memory map.  origin: also return
+    where every variant came from (store_origin)."""
     try:
         reader = StoreReader(path)
     except (OSError, ValueError) as err:
@@ -319,7 +320,11 @@ def load_store(path, dev=0, shard=None):
         matrix.upload_columns(chunk, reader.columns(k, lo, n_local))
         if reader.has_af:
             matrix.set_af(chunk, np.asarray(reader.af(k)))
-    return {"samples": reader.samples, "data": matrix, "var_count": reader.var_count[lo:lo + n_local], "has_af": reader.has_af}
+    data = {"samples": reader.samples, "data": matrix, "var_count": reader.var_count[lo:lo + n_local], "has_af": reader.has_af}
+    if origin:
+        data["origin"] = store_origin(matrix.shape[0], [np.asarray(reader.af(k)) for k in range(len(reader.chunk_vars))]
+                                      if reader.has_af else None)
+    return data
 
 
 class _ChunkBuilder:
@@ -331,13 +336,16 @@ class _ChunkBuilder:
         self.matrix, self.writer, self.calc_af, self.af_as_f32 = matrix, writer, calc_af, af_as_f32
         self.rows, self.af = [], []
         self.chunk_af = []                       # per flushed chunk, kept only while no AF could be set yet
+        self.origin, self.chunk_origin = [], []  # (part, row) of every variant held / flushed: only when asked for (add)
 
     def held_variants(self):
         return sum(len(r) for r in self.rows)
 
-    def add(self, rows, af):
+    def add(self, rows, af, origin=None):
         self.rows.append(rows)
         self.af.append(af)
+        if origin is not None:
+            self.origin.append(origin)
 
     def flush(self):
         if not self.rows:
@@ -345,6 +353,9 @@ class _ChunkBuilder:
         rows = self.rows[0] if len(self.rows) == 1 else np.concatenate(self.rows)
         af = self.af[0] if len(self.af) == 1 else np.concatenate(self.af)
         self.rows, self.af = [], []
+        if self.origin:
+            self.chunk_origin.append(self.origin[0] if len(self.origin) == 1 else np.concatenate(self.origin))
+            self.origin = []
         chunk = self.matrix.add_chunk(len(rows))
         self.matrix.upload_rows_packed(chunk, rows)          # bit transpose to columns happens on the GPU
         if self.writer is not None and hasattr(self.writer, "add_rows"):      # hdf5: the packed rows themselves
@@ -354,15 +365,15 @@ class _ChunkBuilder:
         self.chunk_af.append(af)
 
 
-def _place_part(builder, rows, af, n_samples, calc_af, buffer):
+def _place_part(builder, rows, af, n_samples, calc_af, buffer, origin=None):
     """Hand one part's packed rows to the chunk builder: parts are merged while the chunk stays within --maxmem; a part
     too large for one chunk is cut into the largest pieces that fit; `buffer` variants per chunk only when chunking is
     forced (--maxmem 0): chunks are HBM allocations here, not the I/O granularity they are for the reference's hdf5
-    appends."""
+    appends.  origin: int64 (len(rows), 2), the (part, row) each variant came from; it is merged and cut with the rows."""
     if MAXMEM != 0 and is_memsafe((len(rows), n_samples), calc_af):
         if builder.held_variants() and not is_memsafe((builder.held_variants() + len(rows), n_samples), calc_af):
             builder.flush()
-        builder.add(rows, af)
+        builder.add(rows, af, origin)
         return
     builder.flush()
     if MAXMEM != 0:
@@ -371,11 +382,31 @@ def _place_part(builder, rows, af, n_samples, calc_af, buffer):
     else:
         step = max(64, buffer // 64 * 64)
     for lo in range(0, len(rows), step):
-        builder.add(rows[lo:lo + step], af[lo:lo + step])
+        builder.add(rows[lo:lo + step], af[lo:lo + step], None if origin is None else origin[lo:lo + step])
         builder.flush()
 
 
-def load_h5(path, dev=0, shard=None, buffer=32768):
+def part_origin(part, informative):
+    """int64 (k, 2): for the k informative records of input file number `part`, that number and the record's 0-based
+    position in the file (before the records nobody carries were dropped)."""
+    rows = np.flatnonzero(informative).astype(np.int64)
+    return np.stack([np.full(len(rows), part, dtype=np.int64), rows], axis=1)
+
+
+def chunks_origin(chunk_origin, chunk_af):
+    """The builder's per-chunk origins and AF values -> {"part": int32, "row": int64, "af"} in matrix order."""
+    pairs = np.concatenate(chunk_origin) if chunk_origin else np.zeros((0, 2), np.int64)
+    af = np.concatenate(chunk_af) if chunk_af else np.zeros(0, np.float64)
+    return {"part": pairs[:, 0].astype(np.int32), "row": pairs[:, 1].copy(), "af": af}
+
+
+def store_origin(n_variants, chunk_af=None):
+    """A .utm or .hdf5 store is one input whose rows are the matrix's: part 0, row = the position in the store."""
+    af = None if chunk_af is None else (np.concatenate(chunk_af) if len(chunk_af) else np.zeros(0, np.float32))
+    return {"part": np.zeros(n_variants, np.int32), "row": np.arange(n_variants, dtype=np.int64), "af": af}
+
+
+def load_h5(path, dev=0, shard=None, buffer=32768, origin=False):
     """Read the reference's `--lowmem` HDF5 store (h5store.py): its `data` chunks are LZF-decoded and packed on the GPU
     and go through the same chunk builder and upload as the rows of part files.  Unlike part files, all-zero rows stay
     (the reference's variant total is data.shape[0]) and var_count comes from the file (in an AF store a carrier whose
@@ -406,22 +437,26 @@ def load_h5(path, dev=0, shard=None, buffer=32768):
         for chunk, af in enumerate(builder.chunk_af):
             matrix.set_af(chunk, np.asarray(af, dtype=np.float32))
     lo, n_local = matrix.first_sample, matrix.n_local
-    return {"samples": store.samples, "data": matrix, "var_count": store.var_count[lo:lo + n_local], "has_af": has_af}
+    data = {"samples": store.samples, "data": matrix, "var_count": store.var_count[lo:lo + n_local], "has_af": has_af}
+    if origin:
+        data["origin"] = store_origin(matrix.shape[0], builder.chunk_af if has_af else None)
+    return data
 
 
-def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto"):
+def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto", origin=False):
     """Load and concatenate the inputs into one HBM-resident matrix -> {"samples", "data", "var_count", "has_af"}.
 
     lowmem == 1: in_files[0] is an existing packed store.  lowmem == path: the store is (re)created there while
     loading (a .hdf5 path: the reference's own store, its chunks LZF-encoded on the GPU, h5write.py); like the reference's hdf5 it keeps AF as float32, so `--lowmem` + `--af` scores with float32 AF values
     (answer_key/select_af_h5.txt) and the plain path with float64 (select_af.txt).  `buffer` = variants per chunk
-    when chunking is forced (--maxmem 0).
+    when chunking is forced (--maxmem 0).  origin=True adds the key "origin": per informative variant, in matrix order,
+    {"part": index into in_files, "row": record number inside that file, "af": its AF or None} (select --variants-out).
     """
     logging.info("reading %d input file(s)", len(in_files))
     if lowmem == 1:
         if in_files[0].endswith(H5_SUFFIX):
-            return load_h5(in_files[0], dev, shard, buffer)
-        return load_store(in_files[0], dev, shard)
+            return load_h5(in_files[0], dev, shard, buffer, origin)
+        return load_store(in_files[0], dev, shard, origin)
     if shard is not None and shard[1] > 1 and lowmem is not None:
         logging.error("Create the matrix store with a single process, then select from it with several")
         sys.exit(1)
@@ -445,7 +480,7 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
         af = np.asarray(part["AF"], dtype=np.float64).reshape(-1)[informative]
         if len(rows) == 0:
             continue
-        _place_part(builder, rows, af, len(samples), calc_af, buffer)
+        _place_part(builder, rows, af, len(samples), calc_af, buffer, part_origin(number - 1, informative) if origin else None)
         logging.debug("%d of %d files read", number, len(in_files))
     if builder is not None:
         builder.flush()
@@ -461,7 +496,10 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
             matrix.set_af(chunk, af.astype(np.float32) if lowmem is not None else af)
     if writer is not None:
         writer.finish(var_count)
-    return {"samples": samples, "data": matrix, "var_count": var_count, "has_af": bool(calc_af)}
+    data = {"samples": samples, "data": matrix, "var_count": var_count, "has_af": bool(calc_af)}
+    if origin:
+        data["origin"] = chunks_origin(builder.chunk_origin, builder.chunk_af)
+    return data
 
 
 # ---------------------------------------------------------------------------------------------- command line
@@ -505,6 +543,9 @@ def _build_parser():
                         help="how many samples: a fraction of all if < 1, a count if >= 1, every sample if -1 [%(default)s]")
     parser.add_argument("-o", "--out", type=str, default="/dev/stdout", help="TSV destination [stdout]")
     parser.add_argument("--debug", action="store_true", help="debug-level logging")
+    parser.add_argument("--variants-out", type=str, default=None, metavar="FILE.npz",
+                        help="also write, per informative variant, the row at which it was captured (-1: never), with "
+                             "the input file and record it came from (numpy .npz)")
     scoring = parser.add_argument_group("Scoring Arguments")
     scoring.add_argument("--af", action="store_true", help="score variants by allele frequency instead of 1")
     scoring.add_argument("--weights", type=str, default=None, help="two-column TSV: sample, weight")
@@ -561,7 +602,8 @@ def parse_args(args):
     elif stores and not args.lowmem:
         logging.info("Input is a matrix store: reading it directly")
         args.lowmem = 1
-    logging.info("options in effect: %s", json.dumps(vars(args), sort_keys=True))
+    options = {name: value for name, value in vars(args).items() if name != "variants_out" or value is not None}
+    logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
 
 
@@ -576,6 +618,33 @@ def _gather_var_count(transport, local_counts, n_samples):
                            for rank, blob in enumerate(parts)])
 
 
+def capture_ranks(matrix, order, depth=1):
+    """int32 per variant of the whole matrix (chunks in order): the position in `order` at which `depth` of those samples
+    carry it, -1 if never (utm_capture_rank, one pass per chunk)."""
+    ranks = [matrix.capture_rank(chunk, order, depth) for chunk in range(len(matrix.chunk_vars))]
+    return np.concatenate(ranks) if ranks else np.zeros(0, np.int32)
+
+
+def write_variants(path, data, selected, depth, in_files):
+    """select --variants-out: the capture rank of every informative variant under the selected samples in row order, and
+    where the variant came from (data["origin"], load_files(origin=True)); numpy.savez."""
+    names = [str(name) for name in data["samples"]]
+    position = {name: i for i, name in enumerate(names)}
+    order = np.asarray([position[name] for name in selected], dtype=np.int64)
+    origin = data["origin"]
+    arrays = {"rank": capture_ranks(data["data"], order, depth)}
+    if depth > 1:
+        arrays["first_rank"] = capture_ranks(data["data"], order, 1)
+    arrays["part"], arrays["row"] = origin["part"], origin["row"]
+    if origin["af"] is not None:
+        arrays["af"] = origin["af"]
+    arrays["samples"] = np.asarray(selected, dtype=str)
+    arrays["files"] = np.asarray([str(name) for name in in_files], dtype=str)
+    arrays["depth"] = np.int32(depth)
+    np.savez(path, **arrays)
+    logging.info("%s: capture ranks of %d variants under %d selected samples", path, len(arrays["rank"]), len(selected))
+
+
 def select_main(cmdargs):
     """`utmos select`: load, select, write the TSV (header + one flushed line per selected sample, select.py:440-446)."""
     global MAXMEM
@@ -587,6 +656,9 @@ def select_main(cmdargs):
         sys.exit(1)
     if args.depth > 1 and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--depth above 1 needs the whole sample axis on one GPU: run a single process")
+        sys.exit(1)
+    if args.variants_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--variants-out needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
     missing = [path for path in args.in_files if not os.path.exists(path)]
     if missing:
@@ -601,7 +673,7 @@ def select_main(cmdargs):
     else:   # one GPU per rank on a full node (ranks share devices only on smaller test boxes)
         dev = local_rank % device.nat.device_count() if world > 1 else 0
     data = load_files(args.in_files, args.lowmem, args.buffer, args.af, dev, (rank, world) if world > 1 else None,
-                      args.inflate)
+                      args.inflate, **({"origin": True} if args.variants_out else {}))
     matrix = data["data"]
     if not args.brute_force:
         matrix.set_decremental(True)            # exact; same rows (DESIGN.md "Decremental scoring")
@@ -636,10 +708,14 @@ def select_main(cmdargs):
                                      args.seed, args.depth)
             else:
                 rows = run_selection(data, args.count, subset, exclude, weights, depth=args.depth)
+            selected = []
             for row in rows:
                 logging.info("%s selected: %.1f%% of the variants captured", row[0], row[4] * 100)
                 fout.write("\t".join(str(field) for field in row) + "\n")
                 fout.flush()
+                selected.append(row[0])
+        if args.variants_out:
+            write_variants(args.variants_out, data, selected, args.depth, args.in_files)
     finally:
         if transport is not None:
             # nobody unmaps or frees its columns while a peer's last launches may still read them
