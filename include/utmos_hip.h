@@ -246,6 +246,31 @@ int utm_capture_rank(utm_ctx *ctx, int32_t chunk, const int64_t *global_idx, int
  * of n column indices, a depth m in 1..255; rank_out[n_var] as above.  Needs no GPU. */
 int utm_capture_rank_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, const uint32_t *order, uint64_t n,
                           int32_t m, int32_t *rank_out);
+/* ---- swap gains ------------------------------------------------------------------------------- */
+/* For a panel of k samples: gain_out[i * n_samp_total + t] = F(panel - panel[i] + t) - F(panel) for every sample t, where
+ * F = the number of variants (summed over all chunks) that some member carries -- what every exchange of ONE member for
+ * ONE other sample would capture, the move of a 1-swap local search.  gain = g_t + x[i][t] - u_i with u_i = the variants
+ * only member i carries (unique_out[i]: what the panel loses without it), g_t = the variants t carries and no member does
+ * (new_out[t]) and x[i][t] = the variants t carries of those u_i.  No special case: t = panel[i] gives 0, another member
+ * gives -u_i.  *base_out = F(panel).  Two launches per chunk (k_swap_masks: one pass over the panel's columns;
+ * k_swap_pairs: the bit-matrix product of k + 1 masks with every column); *pass_ms = their HIP-event time.
+ * Stateless, exactly as utm_capture_rank: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats and everything the loop caches are neither read nor changed.  Used and
+ * excluded samples are accepted, as members and as candidates.  Rows cleared by an AF of 0 (utm_set_af) have no carriers.
+ * k == 0: *base_out = 0 and nothing else is written.
+ * UTM_EINVAL, with the outputs untouched, for a NULL panel or a NULL gain_out with k > 0, an index out of range or a
+ * duplicate in the panel.  UTM_ESTATE on a context that holds only a shard of the samples or has an exchange set up. */
+int utm_swap_gains(utm_ctx *ctx, const int64_t *panel, int64_t k,
+                   int64_t *gain_out   /* k * n_samp_total, row i = panel[i] leaves */,
+                   int64_t *unique_out /* k: u_i, may be NULL */,
+                   int64_t *new_out    /* n_samp_total: g_t, may be NULL */,
+                   int64_t *base_out   /* F(panel), may be NULL */,
+                   double *pass_ms     /* may be NULL */);
+/* The arithmetic of the two kernels built for the CPU: cols[s * wp + w] of ONE chunk holding n_var <= 64 * wp variants
+ * of n_samp samples, a panel of k column indices; the outputs as above.  Needs no GPU. */
+int utm_swap_gains_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
+                        const uint32_t *panel, uint64_t k, int64_t *gain_out, int64_t *unique_out,
+                        int64_t *new_out, int64_t *base_out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

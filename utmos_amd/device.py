@@ -167,6 +167,21 @@ class DeviceMatrix:
                                              ctypes.byref(ms) if pass_ms else None))
         return (out, ms.value) if pass_ms else out
 
+    def swap_gains(self, panel, pass_ms=False):
+        """(gains, unique, new, base) of a panel (global sample indices): gains[i, t] = F(panel - panel[i] + t) - F(panel)
+        for every sample t (int64, k x n_samples), unique[i] = the variants only member i carries, new[t] = the variants
+        t carries and no member does, base = F(panel) = the variants some member carries.  Stateless: the columns are
+        read, nothing of the selection is read or changed.  pass_ms: the HIP-event time of the launches as a fifth item."""
+        idx = np.ascontiguousarray(panel, dtype=np.int64).reshape(-1)
+        k = len(idx)
+        gains = np.zeros((k, self.n_samples), dtype=np.int64)
+        unique = np.zeros(k, dtype=np.int64)
+        new = np.zeros(self.n_samples, dtype=np.int64)
+        base, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_swap_gains(self._h, _ptr(idx), k, _ptr(gains), _ptr(unique), _ptr(new), ctypes.byref(base),
+                                           ctypes.byref(ms) if pass_ms else None))
+        return (gains, unique, new, base.value, ms.value) if pass_ms else (gains, unique, new, base.value)
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)

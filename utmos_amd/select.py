@@ -7,6 +7,7 @@ utmos/select.py can switch over (what each one answers to is cited; the bodies a
     greedy_select(matrix, total_variant_count, select_count, ...)      utmos/select.py:69-137
     run_selection(data, select_count, subset, exclude, weights)        utmos/select.py:147-195
                   (+ include, mode, seed: a fixed prefix, and SVCollector's topN / random orders, utmos/select.py:140-142)
+    refined_selection(data, select_count, ..., max_swaps)              (no counterpart: greedy + 1-swap local search)
     load_files(in_files, lowmem, buffer, calc_af)                      utmos/select.py:241-321
     parse_sample_lists / parse_weights / parse_args / select_main      utmos/select.py:327-448
 
@@ -273,6 +274,30 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
     logging.info("%d samples included first; the rest in %s order", len(included), mode)
     return _ordered_selection(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, included, mode, seed,
                               depth)
+
+
+def refined_selection(data, select_count=0.02, subset=None, exclude=None, include=None, max_swaps=None, log=None):
+    """select --refine: the greedy panel of run_selection, improved by 1-swaps (refine.refine: samples that were
+    selectable and are not in the panel come in, the --include samples never leave), then the rows of the greedy order
+    WITHIN the refined panel -- what run_selection(subset=panel names, select_count=len(panel)) gives, still a coverage
+    curve.  The plain count only: no AF, weights or depth.  max_swaps: None = until no swap helps.  `log`, a list,
+    receives refine's (swap, out, in, gain, tot_captured) entries."""
+    from .refine import refine
+    matrix = data["data"]
+    names = np.asarray(data["samples"]).astype(str)
+    position = {name: i for i, name in enumerate(names)}
+    first = list(run_selection(data, select_count, subset, exclude, None, include))
+    panel = [position[row[0]] for row in first]
+    if not panel:
+        return
+    pinned = resolve_include(names, include, exclude) if include else ()
+    panel, swaps = refine(matrix, panel, sample_states(names, subset, exclude), pinned, max_swaps)
+    logging.info("refine: %d swaps, %d -> %d variants captured", len(swaps), first[-1][3], swaps[-1][4] if swaps else first[-1][3])
+    if log is not None:
+        log.extend(swaps)
+    states = np.full(len(names), EXCLUDED, dtype=np.uint8)
+    states[panel] = SELECTABLE
+    yield from greedy_select(matrix, np.asarray(data["var_count"]), len(panel), names, states)
 
 
 # ---------------------------------------------------------------------------------------------- ingest
@@ -560,6 +585,12 @@ def _build_parser():
                          help="how samples are chosen: greedy re-scores after every pick; topN takes the best first-"
                               "iteration scores in order; random takes a seeded permutation [%(default)s]")
     scoring.add_argument("--seed", type=int, default=0, help="seed of --mode random [%(default)s]")
+    scoring.add_argument("--refine", type=int, default=0, metavar="N",
+                         help="after the greedy selection, improve the panel by up to N 1-swaps (one selected sample "
+                              "for one unselected, whenever that captures more variants); -1 = until no swap helps; "
+                              "the TSV is then the greedy order within the refined panel [%(default)s: off]")
+    scoring.add_argument("--refine-out", type=str, default=None, metavar="FILE.tsv",
+                         help="with --refine: write the swaps made (swap, out, in, gain, tot_captured)")
     scoring.add_argument("--depth", type=int, default=1,
                          help="every variant counts until this many selected samples carry it (1..255); above 1 "
                               "new_count / tot_captured count units of min(support, depth) and a column at_depth is "
@@ -594,6 +625,18 @@ def parse_args(args):
     if not 1 <= args.depth <= MAX_DEPTH:
         logging.error("--depth must be between 1 and %d", MAX_DEPTH)
         sys.exit(1)
+    if args.refine < -1:
+        logging.error("--refine takes a number of swaps, or -1 for as many as help")
+        sys.exit(1)
+    if args.refine_out and not args.refine:
+        logging.error("--refine-out needs --refine")
+        sys.exit(1)
+    if args.refine:                              # 1-swaps are judged by the plain count of captured variants
+        clash = ("--af" if args.af else "--weights" if args.weights else "--depth above 1" if args.depth > 1 else
+                 f"--mode {args.mode}" if args.mode != "greedy" else None)
+        if clash:
+            logging.error("--refine improves the plain number of captured variants and cannot be combined with %s", clash)
+            sys.exit(1)
     if not args.in_files and not args.lowmem:
         logging.error("Nothing to read: give input files, or --lowmem STORE to select from an existing store")
         sys.exit(1)
@@ -602,7 +645,8 @@ def parse_args(args):
     elif stores and not args.lowmem:
         logging.info("Input is a matrix store: reading it directly")
         args.lowmem = 1
-    options = {name: value for name, value in vars(args).items() if name != "variants_out" or value is not None}
+    options = {name: value for name, value in vars(args).items()
+               if (name != "variants_out" or value is not None) and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
 
@@ -660,6 +704,9 @@ def select_main(cmdargs):
     if args.variants_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--variants-out needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
+    if args.refine and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--refine needs the whole sample axis on one GPU: run a single process")
+        sys.exit(1)
     missing = [path for path in args.in_files if not os.path.exists(path)]
     if missing:
         logging.error("Input %s does not exist", missing[0])
@@ -683,6 +730,9 @@ def select_main(cmdargs):
         sys.exit(1)
     if data["has_af"] and not args.af:
         logging.critical("The store was created with --af and scores by allele frequency: add --af or recreate it")
+        if args.refine:
+            logging.error("--refine improves the plain number of captured variants and cannot run on a store made with --af")
+            sys.exit(1)
 
     transport = None
     if world > 1:
@@ -703,7 +753,11 @@ def select_main(cmdargs):
     try:
         with open(args.out, "w") as fout:
             fout.write(HEADER_DEPTH if args.depth > 1 else HEADER)
-            if ordered:
+            swaps = []
+            if args.refine:
+                rows = refined_selection(data, args.count, subset, exclude, parse_sample_lists(args.include),
+                                         None if args.refine < 0 else args.refine, swaps)
+            elif ordered:
                 rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
                                      args.seed, args.depth)
             else:
@@ -714,6 +768,9 @@ def select_main(cmdargs):
                 fout.write("\t".join(str(field) for field in row) + "\n")
                 fout.flush()
                 selected.append(row[0])
+        if args.refine_out:
+            from .refine import write_log
+            write_log(args.refine_out, swaps, [str(name) for name in data["samples"]])
         if args.variants_out:
             write_variants(args.variants_out, data, selected, args.depth, args.in_files)
     finally:
