@@ -271,6 +271,32 @@ int utm_swap_gains(utm_ctx *ctx, const int64_t *panel, int64_t k,
 int utm_swap_gains_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
                         const uint32_t *panel, uint64_t k, int64_t *gain_out, int64_t *unique_out,
                         int64_t *new_out, int64_t *base_out);
+/* ---- pair counts ------------------------------------------------------------------------------- */
+/* For a list of n samples: out[i * n + j] = the variants (summed over all chunks) that global_idx[i] and global_idx[j]
+ * both carry and no sample of `given` carries; the diagonal is each sample's own count under that mask.  Symmetric.
+ * Per chunk one k_swap_masks launch over the `given` columns (none without a `given` list: there is no mask then) and
+ * one k_pair_counts launch: a bit-matrix product of the list with itself over 64 x 64 block pairs, both operands staged
+ * in LDS, only the blocks on and above the diagonal computed.  *pass_ms = the launches' HIP-event time.
+ * tile_groups: 0 = automatic (about 8,192 workgroups over the block pairs); above 0 = that many groups of 4 KiB variant
+ * tiles per block pair, clamped to the tile count and raised where a workgroup would walk more than 32,768 tiles.  It
+ * moves the launch shape only and never changes a result.
+ * Stateless, exactly as utm_swap_gains: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats and everything the loop caches are neither read nor changed.  Used and
+ * excluded samples are accepted in both lists; a sample in both has an all-zero row.  Rows cleared by an AF of 0
+ * (utm_set_af) have no carriers.  n == 0 writes nothing.
+ * UTM_EINVAL, with `out` untouched, for a NULL list with a nonzero length, a NULL out with n > 0, an index out of range or
+ * a duplicate within either list.  UTM_ENOMEM when the n x n device buffer cannot be had.  UTM_ESTATE on a context that
+ * holds only a shard of the samples or has an exchange set up. */
+int utm_pair_counts(utm_ctx *ctx, const int64_t *global_idx, int64_t n,
+                    const int64_t *given, int64_t n_given /* may be NULL / 0 */,
+                    uint32_t tile_groups                  /* 0: automatic */,
+                    int64_t *out                          /* n * n */,
+                    double *pass_ms                       /* may be NULL */);
+/* The arithmetic of the two kernels built for the CPU: cols[s * wp + w] of ONE chunk holding n_var <= 64 * wp variants
+ * of n_samp samples (padding bits zero), a list of n and a `given` list of n_given column indices; out as above.
+ * Needs no GPU. */
+int utm_pair_counts_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
+                         const uint32_t *idx, uint64_t n, const uint32_t *given, uint64_t n_given, int64_t *out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

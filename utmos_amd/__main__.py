@@ -15,6 +15,7 @@ def _usage():
             "usage: python -m utmos_amd COMMAND [OPTIONS]\n\n"
             "  select    pick the samples that capture the most variants (GPU)\n"
             "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser; BGZF inflated on the GPU)\n"
+            "  overlap   count the variants every two samples share (GPU)\n"
             "  version   print the version and exit\n")
 
 
@@ -35,7 +36,13 @@ def _run_convert(options):
     return 0
 
 
-COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert}
+def _run_overlap(options):
+    from .overlap import overlap_main
+    overlap_main(options)
+    return 0
+
+
+COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert, "overlap": _run_overlap}
 
 
 def main(argv=None):

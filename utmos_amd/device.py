@@ -182,6 +182,20 @@ class DeviceMatrix:
                                            ctypes.byref(ms) if pass_ms else None))
         return (gains, unique, new, base.value, ms.value) if pass_ms else (gains, unique, new, base.value)
 
+    def pair_counts(self, indices, given=(), tile_groups=0, pass_ms=False):
+        """int64 (n, n): shared[i, j] = the variants the samples indices[i] and indices[j] (global sample indices) both
+        carry and no sample of `given` carries; the diagonal is each sample's own count under that mask.  Stateless: the
+        columns are read, nothing of the selection is read or changed.  tile_groups moves the launch shape only (0:
+        automatic).  pass_ms: return (shared, HIP-event time of the launches) instead."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        panel = np.ascontiguousarray(given, dtype=np.int64).reshape(-1)
+        n = len(idx)
+        out = np.zeros((n, n), dtype=np.int64)
+        ms = ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_pair_counts(self._h, _ptr(idx), n, _ptr(panel) if len(panel) else None, len(panel),
+                                            int(tile_groups), _ptr(out), ctypes.byref(ms) if pass_ms else None))
+        return (out, ms.value) if pass_ms else out
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)
