@@ -297,6 +297,37 @@ int utm_pair_counts(utm_ctx *ctx, const int64_t *global_idx, int64_t n,
  * Needs no GPU. */
 int utm_pair_counts_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
                          const uint32_t *idx, uint64_t n, const uint32_t *given, uint64_t n_given, int64_t *out);
+/* ---- carrier counts ----------------------------------------------------------------------------- */
+/* For a list of n samples: hist_out[c] = the number of variants of the chunk that exactly c of the samples global_idx[]
+ * carry and no sample of `given` carries -- the site-frequency spectrum of the list, beyond the `given` panel.  The sum
+ * of hist_out is the chunk's n_var minus the variants a `given` sample carries.  count_out[v] = the number of listed
+ * samples that carry variant v, or -1 where a `given` sample carries it.  Either output may be NULL, not both.
+ * One k_swap_masks launch over the `given` columns (none without a `given` list: the mask is then the chunk's valid
+ * bits) and one streaming pass over the listed columns (k_carrier_counts): the counts live in registers as bit planes,
+ * 16 columns are folded in at a time by carry-save adders, bins 0..7 are popcounts of plane combinations and only the
+ * variants with a higher count are decoded one by one.  *pass_ms = the launches' HIP-event time.
+ * hist_mode: 0 = automatic, 1 = the decoded variants meet in LDS bins first (n + 1 <= 4,096 bins), 2 = they go to the
+ * global bins directly.  It moves the launch shape only and never changes a result.
+ * Stateless, exactly as utm_capture_rank: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats and everything the loop caches are neither read nor changed.  Used and
+ * excluded samples are accepted in both lists; a sample in both contributes nothing, because its variants are masked.
+ * Rows cleared by an AF of 0 (utm_set_af) have no carriers: they fall in bin 0.  n == 0: hist_out[0] is everything not
+ * masked.
+ * UTM_EINVAL, with both outputs untouched, for a NULL list with a nonzero length, both outputs NULL, a chunk or an index
+ * out of range, a duplicate within either list, hist_mode above 2 or 1 with more than 4,096 bins, or n above 2^20 - 1.
+ * UTM_ESTATE on a context that holds only a shard of the samples or has an exchange set up. */
+int utm_carrier_counts(utm_ctx *ctx, int32_t chunk, const int64_t *global_idx, int64_t n,
+                       const int64_t *given, int64_t n_given /* may be NULL / 0 */,
+                       uint32_t hist_mode                    /* 0 automatic, 1 LDS bins, 2 global bins */,
+                       int64_t *hist_out                     /* n + 1, written (not added to); may be NULL */,
+                       int32_t *count_out                    /* n_var of the chunk; may be NULL */,
+                       double *pass_ms                       /* may be NULL */);
+/* The arithmetic of the kernels built for the CPU, block of 16 columns by block: cols[s * wp + w] of ONE chunk holding
+ * n_var <= 64 * wp variants of n_samp samples (padding bits zero), a list of n and a `given` list of n_given column
+ * indices; hist_out[n + 1] and count_out[n_var] as above.  Needs no GPU. */
+int utm_carrier_counts_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
+                            const uint32_t *idx, uint64_t n, const uint32_t *given, uint64_t n_given,
+                            int64_t *hist_out, int32_t *count_out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

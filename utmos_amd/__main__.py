@@ -16,6 +16,7 @@ def _usage():
             "  select    pick the samples that capture the most variants (GPU)\n"
             "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser; BGZF inflated on the GPU)\n"
             "  overlap   count the variants every two samples share (GPU)\n"
+            "  spectrum  carrier-count histogram of a sample list and its exact random-panel curve (GPU)\n"
             "  version   print the version and exit\n")
 
 
@@ -42,7 +43,14 @@ def _run_overlap(options):
     return 0
 
 
-COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert, "overlap": _run_overlap}
+def _run_spectrum(options):
+    from .spectrum import spectrum_main
+    spectrum_main(options)
+    return 0
+
+
+COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert, "overlap": _run_overlap,
+            "spectrum": _run_spectrum}
 
 
 def main(argv=None):

@@ -196,6 +196,29 @@ class DeviceMatrix:
                                             int(tile_groups), _ptr(out), ctypes.byref(ms) if pass_ms else None))
         return (out, ms.value) if pass_ms else out
 
+    def carrier_counts(self, indices, given=(), counts=False, hist_mode=0, pass_ms=False):
+        """int64 (n + 1): hist[c] = the variants (summed over all chunks) that exactly c of the samples `indices` (global
+        sample indices) carry and no sample of `given` carries.  counts: also the list of per-chunk int32 arrays, the
+        count of every variant, -1 where a `given` sample carries it.  Stateless: the columns are read, nothing of the
+        selection is read or changed.  hist_mode moves the launch shape only (0: automatic, 1: LDS bins, 2: global
+        bins).  pass_ms: also the summed HIP-event time of the launches.  Returns hist, or (hist[, counts][, ms])."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        panel = np.ascontiguousarray(given, dtype=np.int64).reshape(-1)
+        hist, per_chunk, total_ms = np.zeros(len(idx) + 1, dtype=np.int64), [], 0.0
+        for chunk, n_var in enumerate(self.chunk_vars):
+            part = np.zeros(len(idx) + 1, dtype=np.int64)
+            count = np.empty(n_var, dtype=np.int32) if counts else None
+            ms = ctypes.c_double(0.0)
+            nat.check(nat.lib().utm_carrier_counts(self._h, chunk, _ptr(idx) if len(idx) else None, len(idx),
+                                                   _ptr(panel) if len(panel) else None, len(panel), int(hist_mode), _ptr(part),
+                                                   _ptr(count), ctypes.byref(ms) if pass_ms else None))
+            hist += part
+            total_ms += ms.value
+            if counts:
+                per_chunk.append(count)
+        out = (hist,) + ((per_chunk,) if counts else ()) + ((total_ms,) if pass_ms else ())
+        return out if len(out) > 1 else hist
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)
