@@ -328,6 +328,44 @@ int utm_carrier_counts(utm_ctx *ctx, int32_t chunk, const int64_t *global_idx, i
 int utm_carrier_counts_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
                             const uint32_t *idx, uint64_t n, const uint32_t *given, uint64_t n_given,
                             int64_t *hist_out, int32_t *count_out);
+/* ---- group curves ------------------------------------------------------------------------------- */
+#define UTM_GROUPS_MAX 64
+/* For a group id per sample (group_of[s] in 0..n_groups-1, or -1 = in no group) and a list of n samples: with U_g = the
+ * variants of the chunk that some sample of group g carries, multi = the variants in two or more U_g and P_g = U_g &
+ * ~multi (the group's private variants; ungrouped samples play no part in it),
+ *     new_out[g * n + j]  = the variants of U_g whose first carrier in the list is global_idx[j] (utm_capture_rank == j
+ *                           at m = 1): what the sample at position j adds to group g's captured variants,
+ *     priv_out[g * n + j] = the same over P_g,
+ *     total_out[g] = |U_g|, ptotal_out[g] = |P_g|.
+ * A group's never-captured count is total - sum_j new.  A group id without samples has an empty U_g.  The list may hold
+ * ungrouped samples.  Two launches: k_group_unions, one pass over the columns of all grouped samples (sorted by group on
+ * the host) that writes the G union masks and multi and sums the totals; k_group_curve, the walk of k_capture_rank at
+ * m = 1 over the list, which reads the masks only where a position captures something.  *pass_ms = the launches'
+ * HIP-event time.  n == 0: only the first launch, only the totals are written.  priv_out == NULL: the private bins are
+ * not computed and multi is not read by the second launch.
+ * bin_mode: 0 = automatic, 1 = the first positions of the list meet in LDS bins (as many as 8,192 bins hold for
+ * n_groups, or twice n_groups with priv_out, bin rows; the rest go to the global bins), 2 = global bins only.  It moves
+ * the launch shape only and never changes a result.
+ * Stateless, exactly as utm_capture_rank: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats and everything the loop caches are neither read nor changed.  Used and
+ * excluded samples are accepted.  Rows cleared by an AF of 0 (utm_set_af) have no carriers.
+ * UTM_EINVAL, with every output untouched, for a NULL group_of or total_out, a NULL global_idx or new_out with n > 0,
+ * n_groups outside 1..64, a group id outside -1..n_groups-1, a chunk or an index out of range, a duplicate in the list,
+ * or bin_mode above 2.  UTM_ENOMEM when the (n_groups + 1) x wp mask buffer cannot be had.  UTM_ESTATE on a context that
+ * holds only a shard of the samples or has an exchange set up. */
+int utm_group_curve(utm_ctx *ctx, int32_t chunk, const int32_t *group_of /* n_samp_total */, int32_t n_groups,
+                    const int64_t *global_idx, int64_t n, uint32_t bin_mode /* 0 automatic, 1 LDS head, 2 global only */,
+                    int64_t *new_out    /* n_groups * n */,
+                    int64_t *priv_out   /* same, may be NULL */,
+                    int64_t *total_out  /* n_groups */,
+                    int64_t *ptotal_out /* n_groups, may be NULL */,
+                    double *pass_ms     /* may be NULL */);
+/* The arithmetic of the two kernels built for the CPU, word by word: cols[s * wp + w] of ONE chunk holding n_var <=
+ * 64 * wp variants of n_samp samples (padding bits zero), group_of[n_samp], a list of n column indices; the outputs as
+ * above.  Needs no GPU. */
+int utm_group_curve_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
+                         const int32_t *group_of, int32_t n_groups, const uint32_t *order, uint64_t n,
+                         int64_t *new_out, int64_t *priv_out, int64_t *total_out, int64_t *ptotal_out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

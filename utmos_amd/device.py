@@ -219,6 +219,37 @@ class DeviceMatrix:
         out = (hist,) + ((per_chunk,) if counts else ()) + ((total_ms,) if pass_ms else ())
         return out if len(out) > 1 else hist
 
+    def group_curve(self, group_of, n_groups, order, private=True, bin_mode=0, pass_ms=False):
+        """(new, priv, total, ptotal), summed over all chunks: new[g, j] = the variants some sample of group g carries
+        whose first carrier in `order` (global sample indices) stands at position j, priv[g, j] the same over the variants
+        no other group carries, total[g] / ptotal[g] = how many of either kind there are (int64; group_of: one id in
+        0..n_groups-1 per sample, -1 = in no group).  private=False: priv and ptotal are None and are not computed.
+        Stateless: the columns are read, nothing of the selection is read or changed.  bin_mode moves the launch shape
+        only (0: automatic, 1: LDS head bins, 2: global bins).  pass_ms: the summed HIP-event time as a fifth item."""
+        groups = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
+        if groups.shape != (self.n_samples,):
+            raise ValueError(f"group_of must have {self.n_samples} entries")
+        idx = np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
+        n, G = len(idx), int(n_groups)
+        shape = (max(G, 0), n)
+        new, total = np.zeros(shape, np.int64), np.zeros(shape[0], np.int64)
+        priv, ptotal = (np.zeros(shape, np.int64), np.zeros(shape[0], np.int64)) if private else (None, None)
+        total_ms = 0.0
+        for chunk in range(len(self.chunk_vars)):
+            part = [np.zeros(shape, np.int64), np.zeros(shape, np.int64) if private else None,
+                    np.zeros(shape[0], np.int64), np.zeros(shape[0], np.int64) if private else None]
+            ms = ctypes.c_double(0.0)
+            nat.check(nat.lib().utm_group_curve(self._h, chunk, _ptr(groups), G, _ptr(idx) if n else None, n, int(bin_mode),
+                                                _ptr(part[0]), _ptr(part[1]), _ptr(part[2]), _ptr(part[3]),
+                                                ctypes.byref(ms) if pass_ms else None))
+            new += part[0]
+            total += part[2]
+            if private:
+                priv += part[1]
+                ptotal += part[3]
+            total_ms += ms.value
+        return (new, priv, total, ptotal) + ((total_ms,) if pass_ms else ())
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)

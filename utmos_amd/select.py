@@ -212,6 +212,59 @@ def _ordered_selection(matrix, total_variant_count, rounds, names, states, vecto
     yield from fixed_order_rows(matrix, total_variant_count, order[:left], names, states, captured, depth)
 
 
+def _quota_selection(matrix, total_variant_count, rounds, names, states, vector, included, mode, seed, group_of, quota):
+    """Rows of a selection in which no group (group_of: an id per sample, -1 = none) gets more than `quota` samples, the
+    --include prefix counted: the greedy over the samples whose group is not full (the partition-matroid greedy).  The
+    device loop runs for as many iterations as no group can fill in (groups.quota_run_length); then the rest of every full
+    group is marked excluded and the loop restarts from the mask, as after an include prefix.  topN / random: the fixed
+    order with the samples of a full group skipped."""
+    from . import groups
+    n_variants = matrix.shape[0]
+    if n_variants == 0:
+        logging.warning("No informative variants: nothing to select")
+        return
+    taken = groups.group_taken(group_of, int(group_of.max()) + 1, included)
+    captured = 0
+    if len(included):
+        matrix.set_state(states)
+        matrix.set_weights(vector)
+        if getattr(matrix, "coverage_depth", 1) != 1:
+            matrix.set_depth(1)
+        matrix.reset()
+        captured = yield from fixed_order_rows(matrix, total_variant_count, included, names, states)
+    left = rounds - len(included)
+    if left <= 0 or captured >= n_variants:
+        return
+    if mode != "greedy":
+        if not len(included):
+            matrix.set_state(states)
+            matrix.set_weights(vector)
+            if getattr(matrix, "coverage_depth", 1) != 1:
+                matrix.set_depth(1)
+            matrix.reset()
+        order = topn_order(matrix.peek_scores()[1], states) if mode == "topN" else random_order(states, seed)
+        order = groups.quota_filter(order, group_of, taken, quota, left)
+        if len(order) < left:
+            logging.warning("Only %d samples left to take in %s order under --group-max", len(order), mode)
+        yield from fixed_order_rows(matrix, total_variant_count, order, names, states, captured)
+        return
+    position = {name: i for i, name in enumerate(names)}
+    while left > 0:
+        groups.close_full_groups(states, group_of, taken, quota)
+        run = groups.quota_run_length(states, group_of, taken, quota, left)
+        made = 0
+        for row in greedy_select(matrix, total_variant_count, run, names, states, vector, captured=captured):
+            made += 1
+            captured = row[3]
+            g = group_of[position[row[0]]]
+            if g >= 0:
+                taken[g] += 1
+            yield row
+        left -= made
+        if made < run:                          # the device loop stopped on its own (and said why)
+            return
+
+
 # ---------------------------------------------------------------------------------------------- set-up
 def resolve_select_count(n_samples, requested):
     """--count: negative = every sample; below 1 = that fraction of the samples, at least one; else a number of
@@ -246,11 +299,12 @@ def weight_vector(names, weights):
 
 
 def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=None, include=None, mode="greedy", seed=0,
-                  depth=1):
+                  depth=1, group_of=None, group_max=None):
     """Prepare a selection over `data` ({"data": DeviceMatrix, "samples", "var_count"}) and return its row generator.
     include: names that come first, in that order, whatever they score (they count towards select_count); mode: how
     the rest is chosen -- greedy, or the fixed orders topN / random (seed); depth: how many selected samples should
-    carry every variant (rows get a sixth field when it is above 1)."""
+    carry every variant (rows get a sixth field when it is above 1); group_of + group_max: a group id per sample (-1 =
+    none) and the most samples any one group may contribute (--include samples count; depth 1 only)."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}")
     if not 1 <= int(depth) <= MAX_DEPTH:
@@ -268,6 +322,17 @@ def run_selection(data, select_count=0.02, subset=None, exclude=None, weights=No
     vector = weight_vector(names, weights)
     if vector is not None:
         logging.info("%d sample weights given", len(weights))
+    if group_max is not None:
+        if group_of is None or int(group_max) < 1 or depth != 1:
+            raise ValueError("group_max needs group_of, a quota of at least 1 and depth 1")
+        from . import groups
+        group_of = np.asarray(group_of, dtype=np.int32)
+        included = resolve_include(names, include, exclude)
+        if (groups.group_taken(group_of, int(group_of.max()) + 1, included) > int(group_max)).any():
+            logging.error("--include already holds more than --group-max %d samples of one group", int(group_max))
+            sys.exit(1)
+        return _quota_selection(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, included, mode, seed,
+                                group_of, int(group_max))
     if not include and mode == "greedy":
         return greedy_select(data["data"], np.asarray(data["var_count"]), rounds, names, states, vector, depth=depth)
     included = resolve_include(names, include, exclude)
@@ -591,6 +656,14 @@ def _build_parser():
                               "the TSV is then the greedy order within the refined panel [%(default)s: off]")
     scoring.add_argument("--refine-out", type=str, default=None, metavar="FILE.tsv",
                          help="with --refine: write the swaps made (swap, out, in, gain, tot_captured)")
+    scoring.add_argument("--groups", type=str, default=None, metavar="FILE",
+                         help="two-column TSV: sample, group (a population label; at most 64 groups)")
+    scoring.add_argument("--groups-out", type=str, default=None, metavar="FILE.tsv",
+                         help="with --groups: write, per row of the selection and group, what the row adds to the variants "
+                              "that group carries and to those only that group carries")
+    scoring.add_argument("--group-max", type=int, default=None, metavar="Q",
+                         help="with --groups: select at most Q samples of any one group (--include samples count; "
+                              "samples in no group are not limited)")
     scoring.add_argument("--depth", type=int, default=1,
                          help="every variant counts until this many selected samples carry it (1..255); above 1 "
                               "new_count / tot_captured count units of min(support, depth) and a column at_depth is "
@@ -637,6 +710,15 @@ def parse_args(args):
         if clash:
             logging.error("--refine improves the plain number of captured variants and cannot be combined with %s", clash)
             sys.exit(1)
+    if (args.groups_out or args.group_max is not None) and not args.groups:
+        logging.error("--groups-out and --group-max need --groups")
+        sys.exit(1)
+    if args.group_max is not None and args.group_max < 1:
+        logging.error("--group-max must be at least 1")
+        sys.exit(1)
+    if args.groups and (args.depth > 1 or args.refine):   # open: DESIGN.md section 15
+        logging.error("--groups cannot be combined with %s", "--depth above 1" if args.depth > 1 else "--refine")
+        sys.exit(1)
     if not args.in_files and not args.lowmem:
         logging.error("Nothing to read: give input files, or --lowmem STORE to select from an existing store")
         sys.exit(1)
@@ -646,7 +728,8 @@ def parse_args(args):
         logging.info("Input is a matrix store: reading it directly")
         args.lowmem = 1
     options = {name: value for name, value in vars(args).items()
-               if (name != "variants_out" or value is not None) and (name not in ("refine", "refine_out") or value)}
+               if (name not in ("variants_out", "groups", "groups_out", "group_max") or value is not None)
+               and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
 
@@ -707,7 +790,10 @@ def select_main(cmdargs):
     if args.refine and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--refine needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
-    missing = [path for path in args.in_files if not os.path.exists(path)]
+    if args.groups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--groups needs the whole sample axis on one GPU: run a single process")
+        sys.exit(1)
+    missing = [path for path in args.in_files + ([args.groups] if args.groups else []) if not os.path.exists(path)]
     if missing:
         logging.error("Input %s does not exist", missing[0])
         sys.exit(1)
@@ -750,6 +836,10 @@ def select_main(cmdargs):
     subset = parse_sample_lists(args.subset)
     exclude = parse_sample_lists(args.exclude)
     weights = parse_weights(args.weights)
+    group_of = group_names = None
+    if args.groups:
+        from . import groups
+        group_of, group_names = groups.parse_groups(args.groups, data["samples"])
     try:
         with open(args.out, "w") as fout:
             fout.write(HEADER_DEPTH if args.depth > 1 else HEADER)
@@ -757,6 +847,9 @@ def select_main(cmdargs):
             if args.refine:
                 rows = refined_selection(data, args.count, subset, exclude, parse_sample_lists(args.include),
                                          None if args.refine < 0 else args.refine, swaps)
+            elif args.group_max is not None:
+                rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
+                                     args.seed, group_of=group_of, group_max=args.group_max)
             elif ordered:
                 rows = run_selection(data, args.count, subset, exclude, weights, parse_sample_lists(args.include), args.mode,
                                      args.seed, args.depth)
@@ -771,6 +864,8 @@ def select_main(cmdargs):
         if args.refine_out:
             from .refine import write_log
             write_log(args.refine_out, swaps, [str(name) for name in data["samples"]])
+        if args.groups_out:
+            groups.write_group_curve(args.groups_out, data, selected, group_of, group_names)
         if args.variants_out:
             write_variants(args.variants_out, data, selected, args.depth, args.in_files)
     finally:
