@@ -366,6 +366,30 @@ int utm_group_curve(utm_ctx *ctx, int32_t chunk, const int32_t *group_of /* n_sa
 int utm_group_curve_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
                          const int32_t *group_of, int32_t n_groups, const uint32_t *order, uint64_t n,
                          int64_t *new_out, int64_t *priv_out, int64_t *total_out, int64_t *ptotal_out);
+/* ---- variant filters ----------------------------------------------------------------------------- */
+/* Keep only the variants of one chunk whose bit is set in keep[] (ceil(n_var/64) words, variant v = bit v&63 of word
+ * v>>6; bits at or above n_var are ignored).  Kept variants keep their order.  Every local column is compacted, the
+ * chunk's AF values (either mode) with it; wp shrinks to the new count's padded width, padding is zero.  *n_kept (may be
+ * NULL) may be 0: the chunk stays in the list, index unchanged, with no variants (and one zero KiB per column).  What the
+ * reference offers instead is filtering the VCF (bcftools view) before `utmos convert` and converting again.
+ * Out of place: the compacted columns are written into a new block (k_filter_prefix: exclusive prefix of the keep words'
+ * popcounts; k_filter_compact: parallel-suffix compress of every word, the pieces merged in LDS), then the old block is
+ * freed -- peak memory is the matrix plus one chunk.  UTM_ENOMEM, with the chunk untouched, when that does not fit.
+ * Afterwards the chunk is in the state utm_add_chunk + an upload of the kept rows + utm_set_af of the kept values would
+ * have left: covered, the depth planes, the decremental copy, the AF tables and everything else derived from the old
+ * columns are dropped and built again by the utm_reset this call implies.  utm_var_count counts the columns as they are
+ * now (rows an earlier utm_set_af cleared for an AF of 0 stay cleared).  A mask that keeps everything changes nothing but
+ * still restarts the loop.  A filtered chunk can be filtered again.  *pass_ms (may be NULL): HIP-event time of the two
+ * launches and the zero fill of the new block.
+ * UTM_EINVAL for a chunk out of range or a NULL keep.  UTM_ESTATE once the columns are exported (utm_p2p_export /
+ * utm_p2p_import / utm_comm_init): the peers have mapped the old column bases.  A shard context before that is fine --
+ * the mask is the same for every shard. */
+int utm_filter_variants(utm_ctx *ctx, int32_t chunk, const uint64_t *keep, uint64_t *n_kept, double *pass_ms);
+/* The same word arithmetic on the host, no GPU call: cols[c * wp + w] holding n_var <= 64 * wp variants of n_cols columns
+ * -> out[c * wp_out + w], written whole (padding zero); *n_kept (may be NULL) = the kept count, which must fit wp_out
+ * words.  What it replaces: as utm_filter_variants. */
+int utm_filter_columns_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_cols,
+                            const uint64_t *keep, uint64_t *out, uint64_t wp_out, uint64_t *n_kept);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

@@ -17,6 +17,7 @@ def _usage():
             "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser; BGZF inflated on the GPU)\n"
             "  overlap   count the variants every two samples share (GPU)\n"
             "  spectrum  carrier-count histogram of a sample list and its exact random-panel curve (GPU)\n"
+            "  filter    keep the variants that pass AF / carrier-count / list criteria and write them as a .utm store (GPU)\n"
             "  version   print the version and exit\n")
 
 
@@ -49,7 +50,13 @@ def _run_spectrum(options):
     return 0
 
 
-COMMANDS = {"select": _run_select, "version": _run_version, "convert": _run_convert, "overlap": _run_overlap,
+def _run_filter(options):
+    from .variant_filter import filter_main
+    filter_main(options)
+    return 0
+
+
+COMMANDS = {"filter": _run_filter, "select": _run_select, "version": _run_version, "convert": _run_convert, "overlap": _run_overlap,
             "spectrum": _run_spectrum}
 
 

@@ -44,6 +44,7 @@ extern "C" int utm_upload_columns(utm_ctx *c, int32_t chunk, uint32_t first_col,
     if (!cols || (u64)first_col + n_cols > c->n_local || stride_words < ch->w)
         return fail(UTM_EINVAL, "bad column range/stride (first %u n %u stride %llu < %llu words)", first_col, n_cols,
                     (u64)stride_words, ch->w);
+    if (ch->w == 0) return UTM_OK;  // (a chunk filtered to nothing, utm_filter_variants: no words to fill)
     HIP_TRY(hipMemcpy2DAsync(ch->cols + (u64)first_col * ch->wp, ch->wp * 8, cols, stride_words * 8, ch->w * 8, n_cols,
                              hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -61,6 +62,7 @@ extern "C" int utm_download_columns(utm_ctx *c, int32_t chunk, uint32_t first_co
     TRY(chunk_of(c, chunk, &ch));
     if (!cols || (u64)first_col + n_cols > c->n_local || stride_words < ch->w)
         return fail(UTM_EINVAL, "bad column range/stride");
+    if (ch->w == 0) return UTM_OK;  // (a chunk filtered to nothing: no words to copy)
     HIP_TRY(hipMemcpy2DAsync(cols, stride_words * 8, ch->cols + (u64)first_col * ch->wp, ch->wp * 8, ch->w * 8, n_cols,
                              hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -80,12 +80,30 @@ class DeviceMatrix:
         array (or slice of whole rows of one) to fill instead of a new one -- large matrices come down in slices."""
         n_cols = self.n_local - first_col if n_cols is None else n_cols
         words = (self.chunk_vars[chunk] + 63) // 64
+        if words == 0:                               # (a chunk filtered to nothing)
+            return np.zeros((n_cols, 0), dtype=np.uint64) if out is None else out
         if out is None:
             out = np.empty((n_cols, words), dtype=np.uint64)
         elif out.dtype != np.uint64 or out.shape != (n_cols, words) or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous uint64 array of shape (n_cols, words)")
         nat.check(nat.lib().utm_download_columns(self._h, chunk, first_col, n_cols, _ptr(out), words))
         return out
+
+    def filter_variants(self, chunk, keep, pass_ms=False):
+        """Keep only the variants of a chunk whose entry in `keep` (boolean, chunk_vars[chunk] entries) is true: every
+        column is compacted on the device, the chunk's AF values with it, and the loop restarts (utm_filter_variants).
+        Returns the kept count, which may be 0 (the chunk stays, empty); pass_ms: (count, HIP-event time) instead."""
+        keep = np.asarray(keep)
+        if keep.dtype != np.bool_ or keep.shape != (self.chunk_vars[chunk],):
+            raise ValueError(f"keep must be a boolean array of {self.chunk_vars[chunk]} entries")
+        words = np.zeros(max(1, (len(keep) + 63) // 64), dtype=np.uint64)
+        packed = np.packbits(keep, bitorder="little")
+        words.view(np.uint8)[:len(packed)] = packed
+        kept, ms = ctypes.c_uint64(0), ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_filter_variants(self._h, int(chunk), _ptr(words), ctypes.byref(kept),
+                                                ctypes.byref(ms) if pass_ms else None))
+        self.chunk_vars[chunk] = int(kept.value)
+        return (int(kept.value), ms.value) if pass_ms else int(kept.value)
 
     def var_count(self):
         out = np.zeros(self.n_local, dtype=np.int64)
@@ -125,6 +143,8 @@ class DeviceMatrix:
             raise TypeError("AF must be float32 or float64")
         if af.shape[0] != self.chunk_vars[chunk]:
             raise ValueError("AF length differs from the chunk's variant count")
+        if af.shape[0] == 0:                         # (a chunk filtered to nothing: one value that is never read)
+            af = np.zeros(1, dtype=af.dtype)
         nat.check(nat.lib().utm_set_af(self._h, chunk, mode, _ptr(af)))
 
     # -- loop

@@ -395,9 +395,32 @@ def _shard_matrix(n_samples, dev, shard):
     return device.DeviceMatrix(n_samples, device=dev, first_sample=first, n_local=n_local)
 
 
-def load_store(path, dev=0, shard=None, origin=False):
+def filter_loaded(matrix, variants, names, chunk_af, origin):
+    """Apply the run's variant filters (variants = (variant_filter.Criteria, subset names, exclude names)) to the loaded
+    matrix, before var_count is taken and the AF is set: one mask per chunk on the host, every column compacted on the
+    GPU.  Returns the per-chunk masks (None: no filter is active); exits with status 1 when a criterion cannot be applied
+    to this input or nothing is left."""
+    if not variants or not variants[0].active:
+        return None
+    from . import variant_filter
+    try:
+        return variant_filter.apply(matrix, variants[0], names, variants[1], variants[2], chunk_af, origin)
+    except variant_filter.FilterError as err:
+        if hasattr(matrix, "close"):
+            matrix.close()
+        logging.error("%s", err)
+        sys.exit(1)
+
+
+def _cut_origin(origin, masks):
+    """A store's origin arrays under the per-chunk masks."""
+    keep = np.concatenate(masks) if masks else np.zeros(0, bool)
+    return {"part": origin["part"][keep], "row": origin["row"][keep], "af": None if origin["af"] is None else origin["af"][keep]}
+
+
+def load_store(path, dev=0, shard=None, origin=False, variants=None):
     """Open a packed store and upload this process's columns, chunk by chunk, from a memory map.  origin: also return
-    where every variant came from (store_origin)."""
+    where every variant came from (store_origin).  variants: the run's variant filters (filter_loaded)."""
     try:
         reader = StoreReader(path)
     except (OSError, ValueError) as err:
@@ -408,12 +431,20 @@ def load_store(path, dev=0, shard=None, origin=False):
     for k, n_var in enumerate(reader.chunk_vars):
         chunk = matrix.add_chunk(n_var)
         matrix.upload_columns(chunk, reader.columns(k, lo, n_local))
-        if reader.has_af:
-            matrix.set_af(chunk, np.asarray(reader.af(k)))
-    data = {"samples": reader.samples, "data": matrix, "var_count": reader.var_count[lo:lo + n_local], "has_af": reader.has_af}
+    chunk_af = [np.asarray(reader.af(k)) for k in range(len(reader.chunk_vars))] if reader.has_af else None
+    var_count = reader.var_count[lo:lo + n_local]
+    where = store_origin(matrix.shape[0], chunk_af) if origin or variants else None
+    masks = filter_loaded(matrix, variants, reader.samples, chunk_af, where)
+    if masks is not None:               # the kept rows' var_count, taken like the store's own: before AF == 0 rows are cleared
+        var_count = matrix.var_count()
+        chunk_af = None if chunk_af is None else [af[mask] for af, mask in zip(chunk_af, masks)]
+        where = _cut_origin(where, masks)
+    if reader.has_af:
+        for chunk, af in enumerate(chunk_af):
+            matrix.set_af(chunk, af)
+    data = {"samples": reader.samples, "data": matrix, "var_count": var_count, "has_af": reader.has_af}
     if origin:
-        data["origin"] = store_origin(matrix.shape[0], [np.asarray(reader.af(k)) for k in range(len(reader.chunk_vars))]
-                                      if reader.has_af else None)
+        data["origin"] = where
     return data
 
 
@@ -496,7 +527,7 @@ def store_origin(n_variants, chunk_af=None):
     return {"part": np.zeros(n_variants, np.int32), "row": np.arange(n_variants, dtype=np.int64), "af": af}
 
 
-def load_h5(path, dev=0, shard=None, buffer=32768, origin=False):
+def load_h5(path, dev=0, shard=None, buffer=32768, origin=False, variants=None):
     """Read the reference's `--lowmem` HDF5 store (h5store.py): its `data` chunks are LZF-decoded and packed on the GPU
     and go through the same chunk builder and upload as the rows of part files.  Unlike part files, all-zero rows stay
     (the reference's variant total is data.shape[0]) and var_count comes from the file (in an AF store a carrier whose
@@ -523,17 +554,25 @@ def load_h5(path, dev=0, shard=None, buffer=32768, origin=False):
         matrix.close()
         logging.error("%s", err)
         sys.exit(1)
-    if has_af:
-        for chunk, af in enumerate(builder.chunk_af):
-            matrix.set_af(chunk, np.asarray(af, dtype=np.float32))
     lo, n_local = matrix.first_sample, matrix.n_local
-    data = {"samples": store.samples, "data": matrix, "var_count": store.var_count[lo:lo + n_local], "has_af": has_af}
+    var_count = store.var_count[lo:lo + n_local]
+    chunk_af = [np.asarray(af, dtype=np.float32) for af in builder.chunk_af] if has_af else None
+    where = store_origin(matrix.shape[0], chunk_af) if origin or variants else None
+    masks = filter_loaded(matrix, variants, store.samples, chunk_af, where)
+    if masks is not None:
+        var_count = matrix.var_count()
+        chunk_af = None if chunk_af is None else [af[mask] for af, mask in zip(chunk_af, masks)]
+        where = _cut_origin(where, masks)
+    if has_af:
+        for chunk, af in enumerate(chunk_af):
+            matrix.set_af(chunk, af)
+    data = {"samples": store.samples, "data": matrix, "var_count": var_count, "has_af": has_af}
     if origin:
-        data["origin"] = store_origin(matrix.shape[0], builder.chunk_af if has_af else None)
+        data["origin"] = where
     return data
 
 
-def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto", origin=False):
+def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=None, inflate="auto", origin=False, variants=None):
     """Load and concatenate the inputs into one HBM-resident matrix -> {"samples", "data", "var_count", "has_af"}.
 
     lowmem == 1: in_files[0] is an existing packed store.  lowmem == path: the store is (re)created there while
@@ -541,12 +580,14 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
     (answer_key/select_af_h5.txt) and the plain path with float64 (select_af.txt).  `buffer` = variants per chunk
     when chunking is forced (--maxmem 0).  origin=True adds the key "origin": per informative variant, in matrix order,
     {"part": index into in_files, "row": record number inside that file, "af": its AF or None} (select --variants-out).
+    variants = (variant_filter.Criteria, subset names, exclude names): the matrix is cut down to the variants that pass
+    (filter_loaded) right after loading -- var_count, the AF and the origin arrays then describe the kept variants only.
     """
     logging.info("reading %d input file(s)", len(in_files))
     if lowmem == 1:
         if in_files[0].endswith(H5_SUFFIX):
-            return load_h5(in_files[0], dev, shard, buffer, origin)
-        return load_store(in_files[0], dev, shard, origin)
+            return load_h5(in_files[0], dev, shard, buffer, origin, variants)
+        return load_store(in_files[0], dev, shard, origin, variants)
     if shard is not None and shard[1] > 1 and lowmem is not None:
         logging.error("Create the matrix store with a single process, then select from it with several")
         sys.exit(1)
@@ -570,7 +611,8 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
         af = np.asarray(part["AF"], dtype=np.float64).reshape(-1)[informative]
         if len(rows) == 0:
             continue
-        _place_part(builder, rows, af, len(samples), calc_af, buffer, part_origin(number - 1, informative) if origin else None)
+        _place_part(builder, rows, af, len(samples), calc_af, buffer,
+                    part_origin(number - 1, informative) if origin or variants else None)
         logging.debug("%d of %d files read", number, len(in_files))
     if builder is not None:
         builder.flush()
@@ -578,6 +620,11 @@ def load_files(in_files, lowmem=None, buffer=32768, calc_af=False, dev=0, shard=
         logging.error("No input files")
         sys.exit(1)
 
+    masks = filter_loaded(matrix, variants, samples, builder.chunk_af,
+                          chunks_origin(builder.chunk_origin, builder.chunk_af) if variants else None)
+    if masks is not None:
+        builder.chunk_af = [af[mask] for af, mask in zip(builder.chunk_af, masks)]
+        builder.chunk_origin = [where[mask] for where, mask in zip(builder.chunk_origin, masks)]
     # var_count before AF == 0 rows are cleared, like select.py:281-284.  (A shard counts its own samples;
     # select_main gathers the shards' parts.)
     var_count = matrix.var_count() if matrix.chunk_vars else np.zeros(matrix.n_local, dtype=np.int64)
@@ -668,6 +715,8 @@ def _build_parser():
                          help="every variant counts until this many selected samples carry it (1..255); above 1 "
                               "new_count / tot_captured count units of min(support, depth) and a column at_depth is "
                               "added [%(default)s]")
+    from . import variant_filter
+    variant_filter.add_arguments(parser)
     memory = parser.add_argument_group("Memory Arguments")
     memory.add_argument("--lowmem", type=str, default=None,
                         help="matrix store to write while loading the inputs (.utm, or the reference's .hdf5), or to "
@@ -727,8 +776,13 @@ def parse_args(args):
     elif stores and not args.lowmem:
         logging.info("Input is a matrix store: reading it directly")
         args.lowmem = 1
+    filters = ("min_af", "max_af", "min_carriers", "max_carriers", "keep_variants", "drop_variants")
+    if args.lowmem not in (None, 1) and any(getattr(args, name) is not None for name in filters):
+        logging.error("The variant filters cannot be combined with writing a --lowmem store: the store holds every variant. "
+                      "Write the store first, or write a filtered one with `filter -o`")
+        sys.exit(1)
     options = {name: value for name, value in vars(args).items()
-               if (name not in ("variants_out", "groups", "groups_out", "group_max") or value is not None)
+               if (name not in ("variants_out", "groups", "groups_out", "group_max") + filters or value is not None)
                and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
@@ -793,7 +847,11 @@ def select_main(cmdargs):
     if args.groups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--groups needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
-    missing = [path for path in args.in_files + ([args.groups] if args.groups else []) if not os.path.exists(path)]
+    from . import variant_filter
+    criteria = variant_filter.Criteria.from_args(args)
+    variant_filter.refuse_several_processes(criteria)
+    lists = [path for path in (args.keep_variants, args.drop_variants) if path]
+    missing = [path for path in args.in_files + ([args.groups] if args.groups else []) + lists if not os.path.exists(path)]
     if missing:
         logging.error("Input %s does not exist", missing[0])
         sys.exit(1)
@@ -805,8 +863,11 @@ def select_main(cmdargs):
         dev = args.device
     else:   # one GPU per rank on a full node (ranks share devices only on smaller test boxes)
         dev = local_rank % device.nat.device_count() if world > 1 else 0
+    subset = parse_sample_lists(args.subset)
+    exclude = parse_sample_lists(args.exclude)
     data = load_files(args.in_files, args.lowmem, args.buffer, args.af, dev, (rank, world) if world > 1 else None,
-                      args.inflate, **({"origin": True} if args.variants_out else {}))
+                      args.inflate, **({"origin": True} if args.variants_out else {}),
+                      **({"variants": (criteria, subset, exclude)} if criteria.active else {}))
     matrix = data["data"]
     if not args.brute_force:
         matrix.set_decremental(True)            # exact; same rows (DESIGN.md "Decremental scoring")
@@ -833,8 +894,6 @@ def select_main(cmdargs):
         if rank != 0:
             args.out = os.devnull
 
-    subset = parse_sample_lists(args.subset)
-    exclude = parse_sample_lists(args.exclude)
     weights = parse_weights(args.weights)
     group_of = group_names = None
     if args.groups:
