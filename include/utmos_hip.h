@@ -366,6 +366,41 @@ int utm_group_curve(utm_ctx *ctx, int32_t chunk, const int32_t *group_of /* n_sa
 int utm_group_curve_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp,
                          const int32_t *group_of, int32_t n_groups, const uint32_t *order, uint64_t n,
                          int64_t *new_out, int64_t *priv_out, int64_t *total_out, int64_t *ptotal_out);
+/* ---- class counts ------------------------------------------------------------------------------- */
+#define UTM_CLASSES_MAX 16384
+/* For a class label per variant of the chunk (class_of[v] in 0..n_classes-1, or -1 = counted nowhere) and a list of
+ * samples: table_out[j * n_classes + c] = the number of variants of class c that sample global_idx[j] carries.  With
+ * class = utm_capture_rank's rank it is every sample's own capture curve under any panel, with class =
+ * utm_carrier_counts' count every sample's own frequency spectrum.  n == 0 (global_idx may be NULL): every sample of the
+ * matrix, in index order, n_samp_total rows; otherwise n rows.  The table is written, not added to.
+ * One launch (k_class_counts) over a grid of (variant tile groups, blocks of min(16, 16384 / n_classes) listed columns):
+ * a workgroup keeps its columns' bins in LDS, walks the set bits of every column word, looks the variant's label up and
+ * adds 1 to the (column, class) bin, and leaves with one 64-bit atomic per non-zero bin.  The work beyond the column loads
+ * is bounded by the set bits, whatever n_classes is.  *pass_ms = the launch's HIP-event time.
+ * tile_groups: 0 = automatic (about 8,192 workgroups over the column blocks); above 0 = that many groups of 4 KiB variant
+ * tiles per column block, clamped to the tile count and raised where a workgroup would walk more than 32,768 tiles.
+ * mode: 0 = automatic, 1 = the bit walk, 2 = reserved for a form that popcounts the most populous classes in front of
+ * the walk, which is not built: it runs the walk too.  Both move the launch shape only and never change a result.
+ * Stateless, exactly as utm_capture_rank: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats and everything the loop caches are neither read nor changed.  Used and
+ * excluded samples are accepted in the list.  Rows cleared by an AF of 0 (utm_set_af) have no carriers: they are counted
+ * for no sample.
+ * UTM_EINVAL, with table_out untouched, for a NULL class_of or table_out, a NULL list with a nonzero length, n_classes
+ * outside 1..16,384, a label outside -1..n_classes-1, a chunk or an index out of range, a duplicate in the list, mode
+ * above 2, or more than 65,535 column blocks.  UTM_ENOMEM when the device buffers (the labels, the n x n_classes table)
+ * cannot be had.  UTM_ESTATE on a context that holds only a shard of the samples or has an exchange set up, as
+ * utm_apply_order. */
+int utm_class_counts(utm_ctx *ctx, int32_t chunk, const int32_t *class_of /* n_var of the chunk */, int32_t n_classes,
+                     const int64_t *global_idx, int64_t n /* NULL / 0: every sample, in index order */,
+                     uint32_t tile_groups /* 0: automatic */,
+                     uint32_t mode        /* 0 automatic, 1 walk only, 2 reserved (walks) */,
+                     int64_t *table_out   /* n_rows * n_classes, written (not added to) */,
+                     double *pass_ms      /* may be NULL */);
+/* The kernel's arithmetic built for the CPU, word by word: cols[s * wp + w] of ONE chunk holding n_var <= 64 * wp
+ * variants of n_samp samples (padding bits zero), class_of[n_var], a list of n column indices (NULL / 0: every column in
+ * index order); table_out as above.  Needs no GPU. */
+int utm_class_counts_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp, const int32_t *class_of,
+                          int32_t n_classes, const uint32_t *idx, uint64_t n, int64_t *table_out);
 /* ---- variant filters ----------------------------------------------------------------------------- */
 /* Keep only the variants of one chunk whose bit is set in keep[] (ceil(n_var/64) words, variant v = bit v&63 of word
  * v>>6; bits at or above n_var are ignored).  Kept variants keep their order.  Every local column is compacted, the

@@ -13,10 +13,12 @@ from . import __version__
 def _usage():
     return (f"Utmos v{__version__} (MI355X build)\n"
             "usage: python -m utmos_amd COMMAND [OPTIONS]\n\n"
-            "  select    pick the samples that capture the most variants (GPU)\n"
+            "  select    pick the samples that capture the most variants (GPU); --samples-out / --represent-out: how much\n"
+            "            of every sample's own variants each row captured\n"
             "  convert   VCF genotypes -> a .jl / .npz part file (GPU parser; BGZF inflated on the GPU)\n"
             "  overlap   count the variants every two samples share (GPU)\n"
-            "  spectrum  carrier-count histogram of a sample list and its exact random-panel curve (GPU)\n"
+            "  spectrum  carrier-count histogram of a sample list and its exact random-panel curve (GPU); --by-sample: every\n"
+            "            sample's own singletons, doubletons, ...\n"
             "  filter    keep the variants that pass AF / carrier-count / list criteria and write them as a .utm store (GPU)\n"
             "  version   print the version and exit\n")
 

@@ -80,6 +80,8 @@ PROTOTYPES = {
     "utm_carrier_counts_host": [_P, _U64, _U64, _U32, _P, _U64, _P, _U64, _P, _P],
     "utm_group_curve": [_P, _I32, _P, _I32, _P, _I64, _U32, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_double)],
     "utm_group_curve_host": [_P, _U64, _U64, _U32, _P, _I32, _P, _U64, _P, _P, _P, _P],
+    "utm_class_counts": [_P, _I32, _P, _I32, _P, _I64, _U32, _U32, _P, ctypes.POINTER(ctypes.c_double)],
+    "utm_class_counts_host": [_P, _U64, _U64, _U32, _P, _I32, _P, _U64, _P],
     "utm_filter_variants": [_P, _I32, _P, ctypes.POINTER(_U64), ctypes.POINTER(ctypes.c_double)],
     "utm_filter_columns_host": [_P, _U64, _U64, _U32, _P, _P, _U64, ctypes.POINTER(_U64)],
     "utm_set_depth": [_P, _I32],

@@ -630,6 +630,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_pair.hip.h"
 #include "host_spectrum.hip.h"
 #include "host_groups.hip.h"
+#include "host_classes.hip.h"
 #include "host_filter.hip.h"
 #include "host_shard.hip.h"
 #include "host_batch.hip.h"

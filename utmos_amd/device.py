@@ -270,6 +270,33 @@ class DeviceMatrix:
             total_ms += ms.value
         return (new, priv, total, ptotal) + ((total_ms,) if pass_ms else ())
 
+    def class_counts(self, classes_per_chunk, n_classes, indices=None, tile_groups=0, mode=0, pass_ms=False):
+        """int64 (n_rows, n_classes), summed over all chunks: table[j, c] = the variants of class c that sample indices[j]
+        (global sample indices; None: every sample, in index order) carries.  classes_per_chunk: one int32 array per
+        chunk, a label in 0..n_classes-1 per variant or -1 = counted nowhere.  Stateless: the columns are read, nothing
+        of the selection is read or changed.  tile_groups and mode move the launch shape only (0: automatic).  pass_ms:
+        return (table, summed HIP-event time of the launches) instead."""
+        if len(classes_per_chunk) != len(self.chunk_vars):
+            raise ValueError(f"{len(classes_per_chunk)} label arrays for {len(self.chunk_vars)} chunks")
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if idx is not None and len(idx) == 0:
+            return (np.zeros((0, int(n_classes)), np.int64), 0.0) if pass_ms else np.zeros((0, int(n_classes)), np.int64)
+        rows = self.n_samples if idx is None else len(idx)
+        table, total_ms = np.zeros((rows, max(int(n_classes), 0)), dtype=np.int64), 0.0
+        for chunk, n_var in enumerate(self.chunk_vars):
+            labels = np.ascontiguousarray(classes_per_chunk[chunk], dtype=np.int32).reshape(-1)
+            if len(labels) != n_var:
+                raise ValueError(f"chunk {chunk}: {len(labels)} labels for {n_var} variants")
+            if n_var == 0:                               # (a chunk filtered to nothing: one label that is never read)
+                labels = np.full(1, -1, dtype=np.int32)
+            part = np.zeros_like(table)
+            ms = ctypes.c_double(0.0)
+            nat.check(nat.lib().utm_class_counts(self._h, chunk, _ptr(labels), int(n_classes), _ptr(idx), 0 if idx is None else len(idx),
+                                                 int(tile_groups), int(mode), _ptr(part), ctypes.byref(ms) if pass_ms else None))
+            table += part
+            total_ms += ms.value
+        return (table, total_ms) if pass_ms else table
+
     def peek_scores(self):
         counts = np.zeros(self.n_local, dtype=np.int64)
         scores = np.zeros(self.n_local, dtype=np.float64)

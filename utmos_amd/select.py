@@ -30,6 +30,7 @@ from .store import StoreReader, StoreWriter
 MAXMEM = 2  # GB one HBM chunk of packed columns may take; 0 = smallest chunks (the reference's test hook, select.py:18-19)
 
 HEADER = "sample\tvar_count\tnew_count\ttot_captured\tpct_captured\n"
+MAX_PANEL = 16383   # --samples-out / --represent-out: UTM_CLASSES_MAX - 1 rows + the class of the never-captured variants
 HEADER_DEPTH = HEADER[:-1] + "\tat_depth\n"   # --depth M > 1: + variants that M selected samples carry
 MAX_DEPTH = 255
 
@@ -683,6 +684,13 @@ def _build_parser():
     parser.add_argument("--variants-out", type=str, default=None, metavar="FILE.npz",
                         help="also write, per informative variant, the row at which it was captured (-1: never), with "
                              "the input file and record it came from (numpy .npz)")
+    parser.add_argument("--samples-out", type=str, default=None, metavar="FILE.npz",
+                        help="also write, for EVERY sample of the inputs, how many of its own variants each row captured "
+                             "(new, n x k), how many no row did (missed) and how many it carries (total), with samples and "
+                             "panel (numpy .npz)")
+    parser.add_argument("--represent-out", type=str, default=None, metavar="FILE.tsv",
+                        help="also write, per row, how well the panel so far holds the samples outside it: n_outside, and "
+                             "the mean, median and minimum share of a sample's own variants captured")
     scoring = parser.add_argument_group("Scoring Arguments")
     scoring.add_argument("--af", action="store_true", help="score variants by allele frequency instead of 1")
     scoring.add_argument("--weights", type=str, default=None, help="two-column TSV: sample, weight")
@@ -768,6 +776,9 @@ def parse_args(args):
     if args.groups and (args.depth > 1 or args.refine):   # open: DESIGN.md section 15
         logging.error("--groups cannot be combined with %s", "--depth above 1" if args.depth > 1 else "--refine")
         sys.exit(1)
+    if (args.samples_out or args.represent_out) and args.count >= 1 and int(args.count) > MAX_PANEL:
+        logging.error("--samples-out and --represent-out hold a panel of at most %d rows (-c %d asks for more)", MAX_PANEL, int(args.count))
+        sys.exit(1)
     if not args.in_files and not args.lowmem:
         logging.error("Nothing to read: give input files, or --lowmem STORE to select from an existing store")
         sys.exit(1)
@@ -782,7 +793,7 @@ def parse_args(args):
                       "Write the store first, or write a filtered one with `filter -o`")
         sys.exit(1)
     options = {name: value for name, value in vars(args).items()
-               if (name not in ("variants_out", "groups", "groups_out", "group_max") + filters or value is not None)
+               if (name not in ("variants_out", "samples_out", "represent_out", "groups", "groups_out", "group_max") + filters or value is not None)
                and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
@@ -806,14 +817,22 @@ def capture_ranks(matrix, order, depth=1):
     return np.concatenate(ranks) if ranks else np.zeros(0, np.int32)
 
 
-def write_variants(path, data, selected, depth, in_files):
+def selected_order(data, selected):
+    """The global sample indices of the selected names, in row order."""
+    position = {str(name): i for i, name in enumerate(data["samples"])}
+    return np.asarray([position[name] for name in selected], dtype=np.int64)
+
+
+def write_variants(path, data, selected, depth, in_files, ranks=None):
     """select --variants-out: the capture rank of every informative variant under the selected samples in row order, and
-    where the variant came from (data["origin"], load_files(origin=True)); numpy.savez."""
+    where the variant came from (data["origin"], load_files(origin=True)); numpy.savez.  ranks: the per-chunk ranks at
+    `depth`, when the caller has them already."""
     names = [str(name) for name in data["samples"]]
     position = {name: i for i, name in enumerate(names)}
     order = np.asarray([position[name] for name in selected], dtype=np.int64)
     origin = data["origin"]
-    arrays = {"rank": capture_ranks(data["data"], order, depth)}
+    arrays = {"rank": capture_ranks(data["data"], order, depth) if ranks is None else
+              (np.concatenate(ranks) if ranks else np.zeros(0, np.int32))}
     if depth > 1:
         arrays["first_rank"] = capture_ranks(data["data"], order, 1)
     arrays["part"], arrays["row"] = origin["part"], origin["row"]
@@ -840,6 +859,9 @@ def select_main(cmdargs):
         sys.exit(1)
     if args.variants_out and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--variants-out needs the whole sample axis on one GPU: run a single process")
+        sys.exit(1)
+    if (args.samples_out or args.represent_out) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        logging.error("--samples-out and --represent-out need the whole sample axis on one GPU: run a single process")
         sys.exit(1)
     if args.refine and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--refine needs the whole sample axis on one GPU: run a single process")
@@ -869,6 +891,14 @@ def select_main(cmdargs):
                       args.inflate, **({"origin": True} if args.variants_out else {}),
                       **({"variants": (criteria, subset, exclude)} if criteria.active else {}))
     matrix = data["data"]
+    per_sample = args.samples_out or args.represent_out
+    if per_sample and args.count < 1 and len(data["samples"]) > MAX_PANEL:    # (a share of the samples, or all of them)
+        wanted = len(data["samples"]) if args.count < 0 else int(len(data["samples"]) * args.count)
+        if wanted > MAX_PANEL:
+            logging.error("--samples-out and --represent-out hold a panel of at most %d rows (-c %s of %d samples asks for %d)",
+                          MAX_PANEL, args.count, len(data["samples"]), wanted)
+            matrix.close()
+            sys.exit(1)
     if not args.brute_force:
         matrix.set_decremental(True)            # exact; same rows (DESIGN.md "Decremental scoring")
     matrix.set_af_exact_scores(False)           # the TSV has no score column: only ambiguous argmaxes need their chains
@@ -925,8 +955,15 @@ def select_main(cmdargs):
             write_log(args.refine_out, swaps, [str(name) for name in data["samples"]])
         if args.groups_out:
             groups.write_group_curve(args.groups_out, data, selected, group_of, group_names)
+        ranks = None
+        if args.variants_out and per_sample:     # both read the capture ranks of the printed order: one pass per chunk
+            order = selected_order(data, selected)
+            ranks = [matrix.capture_rank(chunk, order, args.depth) for chunk in range(len(matrix.chunk_vars))]
         if args.variants_out:
-            write_variants(args.variants_out, data, selected, args.depth, args.in_files)
+            write_variants(args.variants_out, data, selected, args.depth, args.in_files, ranks)
+        if per_sample:
+            from . import samples
+            samples.write_outputs(args.samples_out, args.represent_out, data, selected, args.depth, ranks)
     finally:
         if transport is not None:
             # nobody unmaps or frees its columns while a peer's last launches may still read them

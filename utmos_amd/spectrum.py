@@ -25,6 +25,7 @@ from . import select
 from .overlap import resolve_given
 
 SPECTRUM_HEADER = "carriers\tvariants\tpct\n"
+CLASSES_MAX = 16384                             # UTM_CLASSES_MAX
 CURVE_HEADER = "k\texpected_captured\texpected_new\tpct_captured\n"
 
 
@@ -91,6 +92,9 @@ def _build_parser():
                         help="TSV of the expected coverage of a random panel of k = 1..n listed samples")
     parser.add_argument("--counts-out", type=str, default=None, metavar="FILE.npz",
                         help="per variant: count (int32, -1 under --given), part, row; samples, given, files, hist (numpy .npz)")
+    parser.add_argument("--by-sample", type=str, default=None, metavar="FILE.npz",
+                        help="per listed sample: table[j, c] = the variants sample j carries that exactly c listed samples "
+                             "carry (column 1: its singletons); samples, table (numpy .npz)")
     parser.add_argument("--quorum", type=float, default=0.95, help="soft core: carried by at least this share of the listed samples [%(default)s]")
     parser.add_argument("--debug", action="store_true", help="debug-level logging")
     samples = parser.add_argument_group("Sample Arguments")
@@ -151,10 +155,15 @@ def spectrum_main(cmdargs):
         listed = np.flatnonzero(states == select.SELECTABLE)
         given = resolve_given(names, select.parse_sample_lists(args.given))
         logging.info("%d of %d samples listed, %d given, %d variants", len(listed), len(names), len(given), matrix.shape[0])
-        if args.counts_out:
+        if args.by_sample and len(listed) + 1 > CLASSES_MAX:
+            logging.error("--by-sample holds %d classes: %d listed samples need %d", CLASSES_MAX, len(listed), len(listed) + 1)
+            sys.exit(1)
+        if args.counts_out or args.by_sample:
             hist, counts = matrix.carrier_counts(listed, given, counts=True)
         else:
             hist, counts = matrix.carrier_counts(listed, given), None
+        # the carrier count as class: -1 (a `given` sample carries the variant) stays -1 and is counted nowhere
+        table = matrix.class_counts(counts, len(listed) + 1, listed) if args.by_sample else None
     finally:
         matrix.close()
     found = classes(hist, args.quorum)
@@ -167,6 +176,9 @@ def spectrum_main(cmdargs):
                  row=origin["row"], samples=names[listed], given=names[given],
                  files=np.asarray([str(name) for name in args.in_files], dtype=str), hist=hist)
         logging.info("%s: carrier counts of %d variants among %d samples", args.counts_out, matrix.shape[0], len(listed))
+    if args.by_sample:
+        np.savez(args.by_sample, samples=names[listed], table=table)
+        logging.info("%s: frequency spectra of %d samples", args.by_sample, len(listed))
     with open(args.out, "w") as fout:
         write_spectrum(fout, hist)
     if args.curve_out:
