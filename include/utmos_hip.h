@@ -486,6 +486,29 @@ int utm_set_af_exact_scores(utm_ctx *ctx, int32_t on);
  * nothing else -- *gbps_out = bytes read / stream time.  What the box delivers today, beside the 8 TB/s spec peak: the bench
  * reports it as roofline.stream_calibration_gbps so that box-to-box variance can be told from kernel quality. */
 int utm_stream_calibration(utm_ctx *ctx, int32_t launches, double *gbps_out);
+/* ---- working views of the integer loop ---------------------------------------------------------- */
+/* Integer scores on the only shard (no AF, depth 1, not decremental, no exchange): at a batch boundary the loop may go on
+ * scoring a copy of the columns compacted to the variants that are still uncovered -- same rows bit for bit, fewer bytes per
+ * iteration.  A chunk of V working variants is compacted when V >= min_vars and at most ratio x V of them are uncovered.
+ * mode 0 = off, 1 = on (the default); min_vars = 0 and ratio <= 0 mean the defaults (2^21, 0.5); ratio must be below 1.
+ * The chunks, utm_get_covered and every other entry point see the matrix as it was uploaded.  The call itself drops any
+ * view in use (the buffers stay).  The copy is allocated at the first compaction, kept across utm_reset and freed with
+ * the context; if it does not fit half of the free HBM the context never compacts (utm_compaction_stats.refused). */
+int utm_set_compaction(utm_ctx *ctx, int32_t mode, uint64_t min_vars, double ratio);
+typedef struct utm_compaction_stats {
+    int64_t compactions;    /* compaction passes since the last utm_reset */
+    uint64_t working_vars;  /* variants per column in what the loop scores now, summed over chunks */
+    int64_t pass_bytes;     /* HBM bytes of the compaction and covered-flush passes (part of utm_stats.algo_bytes) */
+    double pass_ms;         /* ... and their HIP-event time */
+    int32_t refused;        /* the copy did not fit half of the free HBM */
+    int32_t mode;
+    uint64_t min_vars;
+    double ratio;
+    int64_t log_iter[16];   /* the first 16 passes: rows out when the pass ran, */
+    uint64_t log_vars[16];  /* variants kept by it, */
+    double log_ms[16];      /* its time (measuring what was left included) */
+} utm_compaction_stats;
+int utm_get_compaction_stats(utm_ctx *ctx, utm_compaction_stats *out);
 /* Switch per-launch HIP-event timing of the scoring kernels on/off (same as UTM_FLAG_PROFILE_EVENTS). */
 int utm_set_profile(utm_ctx *ctx, int32_t on);
 

@@ -41,6 +41,13 @@ class Stats(ctypes.Structure):
                 ("af_table_passes", ctypes.c_int64)]
 
 
+class CompactionStats(ctypes.Structure):
+    _fields_ = [("compactions", ctypes.c_int64), ("working_vars", ctypes.c_uint64), ("pass_bytes", ctypes.c_int64),
+                ("pass_ms", ctypes.c_double), ("refused", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("min_vars", ctypes.c_uint64), ("ratio", ctypes.c_double),
+                ("log_iter", ctypes.c_int64 * 16), ("log_vars", ctypes.c_uint64 * 16), ("log_ms", ctypes.c_double * 16)]
+
+
 EXCHANGE_NAMES = {0: "none", 1: "mailboxes", 2: "rccl", 3: "caller-driven", 4: "rccl-allreduce"}
 
 
@@ -94,6 +101,8 @@ PROTOTYPES = {
     "utm_get_covered": [_P, _I32, _P],
     "utm_get_stats": [_P, ctypes.POINTER(Stats)],
     "utm_set_profile": [_P, _I32],
+    "utm_set_compaction": [_P, _I32, _U64, ctypes.c_double],
+    "utm_get_compaction_stats": [_P, ctypes.POINTER(CompactionStats)],
     "utm_stream_calibration": [_P, _I32, ctypes.POINTER(ctypes.c_double)],
     "utm_set_af_exact_scores": [_P, _I32],
     "utm_set_decremental": [_P, _I32, ctypes.c_double],

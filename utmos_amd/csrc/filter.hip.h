@@ -176,3 +176,32 @@ __global__ __launch_bounds__(256) void k_filter_compact(const u64 *__restrict__ 
         __syncthreads();  // (the images are zero again before the next round's pieces arrive)
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// The integer loop's working view (host_compact.hip.h): the keep mask of a compaction is what is still uncovered, and
+// while a view is scored the chunk's own covered mask is brought up to date from the result rows.
+// ------------------------------------------------------------------------------------------------
+// keep[i] = ~covered[i] for the n_words words that hold variants, the bits at or above n_var clear.
+__global__ __launch_bounds__(256) void k_compact_keep(const u64 *__restrict__ covered, u64 n_words, u64 n_var, u64 *__restrict__ keep)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (u64)gridDim.x * 256) {
+        u64 k = ~covered[i];
+        if (i == n_words - 1 && (n_var & 63)) k &= (1ull << (n_var & 63)) - 1;
+        keep[i] = k;
+    }
+}
+
+// covered |= the columns of the winners of result rows [r0, r1) (global sample indices; this context holds them all):
+// one pass over covered, every thread ORs its word of every winner.
+__global__ __launch_bounds__(256) void k_or_rows(u64 *__restrict__ covered, const u64 *__restrict__ cols, u64 wp, const i64 *__restrict__ res_idx,
+                                                 i64 r0, i64 r1, unsigned first, unsigned n_local)
+{
+    for (u64 w = (u64)blockIdx.x * 256 + threadIdx.x; w < wp; w += (u64)gridDim.x * 256) {
+        u64 acc = covered[w];
+        for (i64 r = r0; r < r1; ++r) {  // (uniform)
+            const i64 s = res_idx[r] - (i64)first;
+            if (s >= 0 && s < (i64)n_local) acc |= cols[(u64)s * wp + w];
+        }
+        covered[w] = acc;
+    }
+}

@@ -66,22 +66,8 @@ extern "C" int utm_filter_variants(utm_ctx *c, int32_t chunk, const uint64_t *ke
         HIP_TRY(hipEventRecord(ev.e0, c->stream));
     }
     if (kept) {
-        if ((ch->wp + UTM_FILTER_TILE_WORDS - 1) / UTM_FILTER_TILE_WORDS > 0x7FFFFFFFull) return fail(UTM_EINVAL, "chunk too large for one compaction launch");
         hipLaunchKernelGGL(k_filter_prefix, dim3(1), dim3(UTM_FILTER_SCAN_THREADS), 0, c->stream, (const u64 *)d_keep.p, w_in, d_prefix.p);
-        // about 16k workgroups: tiles x column groups, a group at least 8 columns so that a lane's masks are worth deriving
-        const u64 tiles = (ch->wp + UTM_FILTER_TILE_WORDS - 1) / UTM_FILTER_TILE_WORDS;
-        const u64 want_groups = std::max<u64>(1, 16384 / tiles);
-        u64 per_group = std::max<u64>({8, (c->n_local + want_groups - 1) / want_groups, ((u64)c->n_local + 65534) / 65535});
-        per_group = round_up(per_group, UTM_FILTER_U);
-        const dim3 grid((unsigned)tiles, (unsigned)((c->n_local + per_group - 1) / per_group));
-        const bool nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)c->n_local * ch->wp * 8 > ((u64)c->tune.nt_min_mb << 20);
-        if (nt)
-            hipLaunchKernelGGL((k_filter_compact<true>), grid, dim3(256), 0, c->stream, (const u64 *)ch->cols, ch->wp, w_in, (const u64 *)d_keep.p,
-                               (const u64 *)d_prefix.p, d_cols.p, wp_out, c->n_local, (unsigned)per_group);
-        else
-            hipLaunchKernelGGL((k_filter_compact<false>), grid, dim3(256), 0, c->stream, (const u64 *)ch->cols, ch->wp, w_in, (const u64 *)d_keep.p,
-                               (const u64 *)d_prefix.p, d_cols.p, wp_out, c->n_local, (unsigned)per_group);
-        HIP_TRY(hipGetLastError());
+        TRY(launch_filter_compact(c, ch->cols, ch->wp, w_in, d_keep.p, d_prefix.p, d_cols.p, wp_out));  // (host_compact.hip.h)
     }
     if (pass_ms) HIP_TRY(hipEventRecord(ev.e1, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

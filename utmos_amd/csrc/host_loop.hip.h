@@ -38,10 +38,11 @@ template <int STEPS>
 static void launch_score_int(utm_ctx *c, const LaunchTimer &t, const Chunk &ch, unsigned blocks, unsigned group, unsigned n_groups,
                              bool nt, const IntLaunch &how)
 {
-    const u64 *cols = ch.cols;
+    const ScoreView v = score_view(ch);  // (the chunk's working view while it has one: host_compact.hip.h)
+    const u64 *cols = v.cols;
     const PickArgs pa = pick_args(c);
 #define UTM_LAUNCH_K(K, NT, FUSED)                                                                                                 \
-    UTM_TIMED_LAUNCH(t, (K<STEPS, NT, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), cols, ch.covered, ch.wp,                 \
+    UTM_TIMED_LAUNCH(t, (K<STEPS, NT, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), cols, v.covered, v.wp,                   \
                      pending_of(c, ch, true), (const IterState *)c->d_st, (const unsigned *)c->d_act, c->d_cnt, group, n_groups,   \
                      how.by_pos ? 1u : 0u, pa)
 #define UTM_LAUNCH_INT(K)                                                                                                          \
@@ -58,7 +59,7 @@ static void launch_score_int(utm_ctx *c, const LaunchTimer &t, const Chunk &ch, 
     // 32 and 16 KiB tiles: the register-quarter form (same unit of work, grid and arrivals) unless UTM_SCORE_FORM=0.
     // Its short last quarter reads the column's last STEPS/4 KiB, so a column shorter than one tile keeps k_score_int.
     if constexpr (STEPS == 32 || STEPS == 16) {
-        if (c->tune.score_form == 1 && ch.wp >= (u64)STEPS * UTM_STEP_WORDS) {
+        if (c->tune.score_form == 1 && v.wp >= (u64)STEPS * UTM_STEP_WORDS) {
             UTM_LAUNCH_INT(k_score_intq)
             return;
         }
@@ -151,10 +152,11 @@ static void launch_score_streaming(utm_ctx *c, const Chunk &ch, unsigned a_ub, b
     // non-temporal column loads when the matrix is a stream far larger than the 256 MB Infinity Cache (+10 % at
     // 3 GB); a matrix that (nearly) fits is better left to the caches (chr22-sized 345 MB: +5 %).  By the matrix, not
     // by the columns still selectable: the tail of a 3 GB select-all run measured slower with cached loads.
-    const bool use_nt = nt_env >= 0 ? nt_env != 0 : (u64)c->n_local * c->col_words * 8 > ((u64)nt_min_mb << 20);
-    const int af_big = tn.af_steps == 32 ? 32 : 16;
+    // (integer scores: by what the loop streams -- the working views, once the chunks have them)
     const bool af = c->af_mode != UTM_AF_NONE;
-    const u64 steps_total = ch.wp / UTM_STEP_WORDS;
+    const bool use_nt = nt_env >= 0 ? nt_env != 0 : (u64)c->n_local * (af ? c->col_words : work_col_words(c)) * 8 > ((u64)nt_min_mb << 20);
+    const int af_big = tn.af_steps == 32 ? 32 : 16;
+    const u64 steps_total = (af ? ch.wp : score_view(ch).wp) / UTM_STEP_WORDS;
     const u64 waves_needed = (a_ub + 3) / 4;  // workgroups if every wave had one sample
     int steps = 2;
     if (af) {
@@ -228,8 +230,8 @@ static LoopShape loop_shape(utm_ctx *c, int af = 0)
         c->n_ranks != 1 || c->n_local != c->n_total || c->comm || c->p2p || c->n_local >= UTM_LOOP_MAX_LOCAL ||
         (tn.persist_max_samples > 0 && c->n_local > (unsigned)tn.persist_max_samples))
         return sh;
-    const Chunk &ch = c->chunks[0];
-    if (tn.persist_max_mb > 0 && (u64)c->n_local * ch.wp * 8 > ((u64)tn.persist_max_mb << 20)) return sh;
+    const u64 wp = af ? c->chunks[0].wp : score_view(c->chunks[0]).wp;  // (integer scores: the working view's columns)
+    if (tn.persist_max_mb > 0 && (u64)c->n_local * wp * 8 > ((u64)tn.persist_max_mb << 20)) return sh;
     static int cus = 0, occ_all[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};  // resident blocks per CU for the 8 / 16 / 32 / 64 KiB tile, integer / AF / AF-interval form
     if (!cus) {
         hipDeviceProp_t prop;
@@ -256,7 +258,7 @@ static LoopShape loop_shape(utm_ctx *c, int af = 0)
     // tile) pair costs one atomic on the position's count word, 16 count words share a cache line, and beyond ~30 tiles
     // those lines become the bottleneck (measured: 2,504 samples, 31 tiles +3.5 %, 39 tiles -2 %, 153 tiles -15 % against
     // one launch per iteration).  A matrix taller than that keeps the launch-per-iteration path.
-    const u64 steps_total = ch.wp / UTM_STEP_WORDS;
+    const u64 steps_total = wp / UTM_STEP_WORDS;
     for (int t = 0; t < 4; ++t) {
         const int steps = 8 << t;
         if (tn.persist_tile_kib > 0 && steps != tn.persist_tile_kib) continue;
@@ -311,6 +313,7 @@ static int loop_af_form(const utm_ctx *c, bool first_is_full)
 static int enqueue_loop(utm_ctx *c, const LoopShape &sh, int k_batch, int af = 0)
 {
     const Chunk &ch = c->chunks[0];
+    const ScoreView v = af ? ScoreView{ch.cols, ch.covered, ch.n_var, ch.w, ch.wp} : score_view(ch);
     if (af && !c->d_loop_w[0]) {  // the AF form's per-position words: two arrival / count-decrease words, two sum-decrease words
         const size_t bytes = ((size_t)c->n_local + UTM_PICK_PAD) * 8;
         for (int i = 0; i < 4; ++i) {
@@ -318,7 +321,7 @@ static int enqueue_loop(utm_ctx *c, const LoopShape &sh, int k_batch, int af = 0
             HIP_TRY(hipMemsetAsync(c->d_loop_w[i], 0, bytes, c->stream));
         }
     }
-    const bool use_nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)c->n_local * c->col_words * 8 > ((u64)c->tune.nt_min_mb << 20);
+    const bool use_nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)c->n_local * (af ? c->col_words : v.wp) * 8 > ((u64)c->tune.nt_min_mb << 20);
     // position claim counters: [3 sets, iteration % 3][tiles][wave index], 128 B apart
     const size_t claim_bytes = (size_t)3 * sh.n_tiles * UTM_LOOP_WAVES * UTM_CLAIM_STRIDE * sizeof(unsigned);
     if (c->claim_bytes < claim_bytes) {
@@ -348,12 +351,12 @@ static int enqueue_loop(utm_ctx *c, const LoopShape &sh, int k_batch, int af = 0
     u64 *w0 = af ? c->d_loop_w[0] : c->d_cnt, *w1 = af ? c->d_loop_w[1] : c->d_cnt_alt;  // (AF: d_cnt holds the per-sample counts)
     if (getenv("UTM_VERBOSE") && c->persist_launches == 0)
         fprintf(stderr, "libutmos_hip: k_loop_int form %d: cols %p..%p covered %p priv %p (wp %llu) af %p afx %p log %p (stride %llu) known %p %p words %p %p %p %p act %p cnt %p afsum %p sync %p claim %p grid %u\n",
-                af, (void *)ch.cols, (void *)(ch.cols + (size_t)c->n_local * ch.wp), (void *)ch.covered, (void *)c->d_loop_priv, (unsigned long long)ch.wp,
+                af, (void *)v.cols, (void *)(v.cols + (size_t)c->n_local * v.wp), (void *)v.covered, (void *)c->d_loop_priv, (unsigned long long)v.wp,
                 (void *)ch.af, (void *)ch.afx, (void *)laf.newly_log, (unsigned long long)c->col_words, (void *)c->d_known_cnt, (void *)c->d_known_val,
                 (void *)c->d_loop_w[0], (void *)c->d_loop_w[1], (void *)c->d_loop_w[2], (void *)c->d_loop_w[3], (void *)c->d_act, (void *)c->d_cnt,
                 (void *)c->d_afsum, (void *)c->d_loop_sync, (void *)c->d_claim, grid.x);
 #define UTM_LAUNCH_LOOP(S, NT, AFF)                                                                                                 \
-    UTM_TIMED_LAUNCH(t, (k_loop_int<S, NT, AFF>), grid, dim3(UTM_LOOP_THREADS), (const u64 *)ch.cols, ch.covered, ch.wp, pending_of(c, ch, true), c->d_st, \
+    UTM_TIMED_LAUNCH(t, (k_loop_int<S, NT, AFF>), grid, dim3(UTM_LOOP_THREADS), v.cols, v.covered, v.wp, pending_of(c, ch, true), c->d_st, \
                      c->d_act, w0, w1, sh.q_slots, c->d_claim, k_batch, c->d_loop_sync, pa, drop, c->tune.persist_claims, c->tune.persist_ahead_ticks, c->tune.persist_ahead0_ticks, laf)
 #define UTM_LAUNCH_LOOP2(S, NT) \
     if (af == 2) UTM_LAUNCH_LOOP(S, NT, 2); \
@@ -498,12 +501,13 @@ static int enqueue_score_decr(utm_ctx *c)
 //                        reads the table as a whole; + the newly-covered mask written once and read once where a
 //                        separate launch makes it (winner columns read in place from another GPU).
 enum { UTM_PASS_PLAIN = 0, UTM_PASS_AF_FULL = 1, UTM_PASS_AF_DELTA = 2 };
-static i64 iteration_bytes(const utm_ctx *c, u64 a, int kind = -1)
+// `brute`: over the chunks as they were uploaded (utm_stats.brute_force_bytes), whatever view the launches read.
+static i64 iteration_bytes(const utm_ctx *c, u64 a, int kind = -1, bool brute = false)
 {
     if (kind < 0) kind = c->af_mode != UTM_AF_NONE ? UTM_PASS_AF_FULL : UTM_PASS_PLAIN;
     i64 b = 0;
     for (auto &ch : c->chunks) {
-        b += (i64)((a + 3) * ch.w * 8);
+        b += (i64)((a + 3) * (brute ? ch.w : score_view(ch).w) * 8);
         if (kind == UTM_PASS_AF_FULL) b += (i64)ch.n_var * (c->af_mode == UTM_AF_F64 && !c->af_fixed ? 8 : 4);
         if (kind == UTM_PASS_AF_DELTA && remote_reads(c)) b += (i64)(2 * ch.w * 8);  // (a folded delta pass has no mask array)
     }
@@ -696,7 +700,14 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
     if (c->af_mode == UTM_AF_NONE) batch = std::min(batch, 256);  // (the persistent loop's record carries an 8-bit iteration tag)
     i64 enq = 0;
     bool tail_deferred = false;  // the last batch left its last row's exact score to the end of the run
+    // working views (host_compact.hip.h): a context that has left the plain integer loop scores its chunks again
+    const bool compacting = compact_eligible(c);
+    if (!compacting) invalidate_views(c);
     while (enq < k_max && !c->finished) {
+        // the host is synchronised here: chunks that have lost enough variants get a (new) compacted view, and while a
+        // chunk may still be compacted the run's first batches are short (compact_policy)
+        int view_batch = UTM_COMPACT_BATCH;
+        if (compacting) TRY(compact_at_boundary(c, &view_batch));
         // AF runs start with short batches: the dense -> sparse kernel switch is taken at a batch boundary
         // ... and so is the switch to decremental iterations
         // (the AF form of the persistent loop needs no host decision inside a batch: 256 iterations per launch, as for integers)
@@ -710,6 +721,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
                                : (c->decr_enabled && c->iter < 64)                          ? std::min<i64>(batch, decr_first)
                                                                                             : batch;
         i64 n = std::min<i64>(this_batch, k_max - enq);
+        if (compacting && batch_env <= 0) n = std::min<i64>(n, view_batch);
         const unsigned a0 = c->active_ub;
         // depth M > 1: covered changes by more than "the winner's column ORed in" (k_depth_apply), so every iteration is a
         // full pass against covered as it stands -- no accumulators are carried from one iteration to the next
@@ -812,7 +824,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
             const int kind = !af_par ? -1 : ((j == 0 && first_is_full) || deep) ? UTM_PASS_AF_FULL : UTM_PASS_AF_DELTA;
             i64 full = iteration_bytes(c, a0 - drop, kind);
             if (deep && j < rows) full += (i64)(2 * c->depth_planes + 3) * (i64)c->col_words * 8;  // k_depth_apply: column, covered and planes in and out
-            c->brute_bytes += full;
+            c->brute_bytes += any_view(c) ? iteration_bytes(c, a0 - drop, kind, /*brute=*/true) : full;
             if (!decr) c->algo_bytes += full;
         }
         if (af_par && rows > 0 && !deep) {
@@ -857,6 +869,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         if (deep && (c->flags & UTM_FLAG_PROFILE_EVENTS)) TRY(collect_depth_times(c));
     }
     if (tail_deferred) TRY(defer_flush_last(c));
+    TRY(flush_views(c));  // the chunks' own covered masks are current at every ABI boundary
     HIP_TRY(hipEventRecord(c->ev_loop1, c->stream));
     HIP_TRY(hipEventSynchronize(c->ev_loop1));
     float ms = 0;
@@ -890,6 +903,7 @@ extern "C" int utm_peek_scores(utm_ctx *c, int64_t *counts, double *scores)
 {
     CTX(c);
     TRY(ensure_prepared(c));
+    if (!compact_eligible(c)) invalidate_views(c);  // (as utm_run: a valid view gives the same counts from fewer bytes)
     // with AF every sample's exact reference score is wanted, so all of them take the sequential chain
     c->keep_valid = false;  // the pending winner gets applied here: the next iteration must re-score in full
     TRY(enqueue_score(c, /*force_sequential=*/true, false, nullptr, /*by_sample=*/true));

@@ -125,6 +125,13 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
     HIP_TRY(hipMemsetAsync(c->d_known_cnt, 0xFF, (size_t)c->n_local * 8, c->stream));  // (a run that ended on an error may have left counts behind)
     for (auto &ch : c->chunks)
         if (restart) HIP_TRY(hipMemsetAsync(ch.covered, 0, ch.wp * 8, c->stream));
+    // the loop scores the chunks themselves again (the views' buffers stay for the next compaction); a chunk has lost at
+    // most what the whole matrix has captured
+    invalidate_views(c);
+    for (auto &ch : c->chunks) {
+        ch.work.known_uncov = ch.n_var;
+        ch.work.known_tot = 0;
+    }
     if (restart) TRY(depth_prepare(c));
     // Samples that start out used cover their variants from the first iteration (select.py:36-39) -- on every
     // shard's covered replica, whoever owns the column: local columns are OR-ed in place; a peer's column is read
@@ -210,6 +217,9 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
         c->af_table_passes = 0;
         c->score_ms = 0;
         c->algo_bytes = 0;
+        c->compactions = 0;
+        c->compact_bytes = 0;
+        c->compact_ms = 0;
     }
     c->prepared = true;
     return UTM_OK;

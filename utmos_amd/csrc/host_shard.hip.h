@@ -20,6 +20,7 @@ extern "C" int utm_local_best(utm_ctx *c, utm_record *rec)
     rec->idx = -1;
     if (c->finished) return UTM_OK;
     c->keep_valid = false;
+    invalidate_views(c);  // (a caller-driven loop scores the chunks themselves)
     TRY(enqueue_score(c));
     PickArgs a = pick_args(c);
     enqueue_candidates(c, a, false);
@@ -52,6 +53,7 @@ extern "C" int utm_apply_records(utm_ctx *c, const utm_record *recs, int32_t n_r
     if (c->comm) return fail(UTM_ESTATE, "context exchanges through RCCL; use utm_step/utm_run");
     TRY(ensure_prepared(c));
     TRY(ensure_xbuf(c, n_ranks));
+    invalidate_views(c);  // (a caller-driven loop scores the chunks themselves)
     // who wins (same rule as decide()) -- only needed to know whether the winner's column has to come with the call
     int win = -1;
     for (int r = 0; r < n_ranks; ++r) {

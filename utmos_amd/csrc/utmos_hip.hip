@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "kernels.hip.h"
+#include "compact_policy.h"
 
 // ---------------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -244,6 +245,21 @@ extern "C" int utm_env_overrides(char *buf, uint64_t cap)
 }
 
 // ---------------------------------------------------------------------------------------- context
+// A chunk's working view: every column compressed to the variants that were uncovered when the copy was made, in the
+// chunk's own layout (cols[s * wp + w], every local sample keeps its index), with a covered mask of its own that starts
+// out empty.  The integer scoring launches take it instead of the chunk while `valid`; everything else keeps reading the
+// chunk.  The buffers outlive utm_reset (the next run compacts into them again) and go with the context.
+struct WorkView {
+    u64 *cols = nullptr, *covered = nullptr;
+    u64 n_var = 0, w = 0, wp = 0;
+    u64 cap_words = 0;        // room of `cols`, in words (+ UTM_COLS_SLACK_BYTES behind them)
+    bool valid = false;
+    u64 *keep = nullptr, *prefix = nullptr;  // the pass's keep words (chunk wp) and their prefix counts (chunk wp + 1)
+    i64 r0 = 0;               // while valid: the winners of result rows below r0 are in the chunk's own covered mask
+    u64 known_uncov = 0;      // the chunk's uncovered variants when `tot` was known_tot (n_var at a reset: an upper bound)
+    i64 known_tot = 0;
+};
+
 struct Chunk {
     u64 n_var = 0;
     u64 w = 0;   // words holding variants
@@ -266,6 +282,7 @@ struct Chunk {
     u64 *rows_t = nullptr;         // decremental scoring: word-interleaved copy [wp][s_t] (optional: needs the room)
     u64 *planes = nullptr;         // coverage depth M > 1: bit_length(M) planes of wp words, plane p = bit p of every variant's support
     bool rows_t_valid = false;
+    WorkView work;                 // integer scoring: the compacted copy the loop scores while it is valid (host_compact.hip.h)
     std::vector<float> h_af32;
     std::vector<double> h_af64;
 };
@@ -404,7 +421,27 @@ struct utm_ctx {
     size_t ev_used = 0;
     double score_ms = 0.0;
     hipEvent_t ev_loop0 = nullptr, ev_loop1 = nullptr;
+
+    // working views of the integer loop (host_compact.hip.h)
+    bool compact_on = true;
+    u64 compact_min_vars = UTM_COMPACT_MIN_VARS;
+    double compact_ratio = UTM_COMPACT_RATIO;
+    bool compact_refused = false;   // the copy did not fit half of the free HBM: this context never compacts
+    i64 compactions = 0;            // since the last utm_reset, as the other statistics
+    i64 compact_bytes = 0;
+    double compact_ms = 0.0;
+    i64 compact_pass_iter[UTM_COMPACT_LOG] = {0};
+    u64 compact_pass_vars[UTM_COMPACT_LOG] = {0};
+    double compact_pass_ms[UTM_COMPACT_LOG] = {0};
+    hipEvent_t ev_cmp0 = nullptr, ev_cmp1 = nullptr;
 };
+
+// The loop scores the chunks themselves again; the views' buffers stay.  Only where the chunks' covered masks are current:
+// at an ABI boundary (utm_run brings them up to date before it returns) or where they are rebuilt anyway (utm_reset).
+static void invalidate_views(utm_ctx *c)
+{
+    for (auto &ch : c->chunks) ch.work.valid = false;
+}
 
 static inline u64 round_up(u64 x, u64 m) { return (x + m - 1) / m * m; }
 
@@ -507,6 +544,8 @@ extern "C" int utm_ctx_create(int device, uint32_t n_samp_total, uint32_t first_
     c->xbuf_ranks = 1;
     HIP_TRY(hipEventCreate(&c->ev_loop0));
     HIP_TRY(hipEventCreate(&c->ev_loop1));
+    HIP_TRY(hipEventCreate(&c->ev_cmp0));
+    HIP_TRY(hipEventCreate(&c->ev_cmp1));
     return UTM_OK;
 }
 
@@ -532,7 +571,10 @@ extern "C" int utm_ctx_destroy(utm_ctx *c)
         (void)hipFree(ch.list_val);
         (void)hipFree(ch.mask);
         (void)hipFree(ch.planes);
+        (void)hipFree(ch.work.cols); (void)hipFree(ch.work.covered); (void)hipFree(ch.work.keep); (void)hipFree(ch.work.prefix);
     }
+    if (c->ev_cmp0) (void)hipEventDestroy(c->ev_cmp0);
+    if (c->ev_cmp1) (void)hipEventDestroy(c->ev_cmp1);
     (void)hipFree(c->d_depth_acc); (void)hipFree(c->d_depth_sync); (void)hipFree(c->d_res_sat);
     for (auto e : c->ev_depth) (void)hipEventDestroy(e);
     (void)hipFree(c->d_cand);
@@ -623,6 +665,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_options.hip.h"
 #include "host_depth.hip.h"
 #include "host_reset.hip.h"
+#include "host_compact.hip.h"
 #include "host_loop.hip.h"
 #include "host_order.hip.h"
 #include "host_rank.hip.h"
