@@ -489,11 +489,18 @@ int utm_stream_calibration(utm_ctx *ctx, int32_t launches, double *gbps_out);
 /* ---- working views of the integer loop ---------------------------------------------------------- */
 /* Integer scores on the only shard (no AF, depth 1, not decremental, no exchange): at a batch boundary the loop may go on
  * scoring a copy of the columns compacted to the variants that are still uncovered -- same rows bit for bit, fewer bytes per
- * iteration.  A chunk of V working variants is compacted when V >= min_vars and at most ratio x V of them are uncovered.
- * mode 0 = off, 1 = on (the default); min_vars = 0 and ratio <= 0 mean the defaults (2^21, 0.5); ratio must be below 1.
+ * iteration.  The first copy of a run is made from the chunk, every later one from the copy before it (two column blocks,
+ * used in turn), and a pass moves only the columns of the samples that are still selectable.
+ * mode 0 = off, 1 = on (the default).  min_vars = 0 and ratio <= 0 (the default): the library decides by cost -- a chunk is
+ * compacted at a batch boundary while one iteration still streams more than stream_bytes from what the loop scores
+ * (selectable samples x bytes per column; what the Infinity Cache would serve is left alone) and the bytes the next batch
+ * would read for nothing exceed pass_cost x the bytes of the pass.  min_vars > 0 or ratio > 0: a chunk of V working
+ * variants is compacted when V >= min_vars and at most ratio x V of them are uncovered (the one left at 0 stands for 2^21 /
+ * 0.5); ratio must be below 1.
  * The chunks, utm_get_covered and every other entry point see the matrix as it was uploaded.  The call itself drops any
- * view in use (the buffers stay).  The copy is allocated at the first compaction, kept across utm_reset and freed with
- * the context; if it does not fit half of the free HBM the context never compacts (utm_compaction_stats.refused). */
+ * view in use (the buffers stay).  The blocks are allocated at the first and the second compaction, kept across utm_reset
+ * and freed with the context; if the first does not fit half of the free HBM the context never compacts
+ * (utm_compaction_stats.refused), if the second does not, the chunk keeps the view it has for that run (view_refused). */
 int utm_set_compaction(utm_ctx *ctx, int32_t mode, uint64_t min_vars, double ratio);
 typedef struct utm_compaction_stats {
     int64_t compactions;    /* compaction passes since the last utm_reset */
@@ -502,11 +509,16 @@ typedef struct utm_compaction_stats {
     double pass_ms;         /* ... and their HIP-event time */
     int32_t refused;        /* the copy did not fit half of the free HBM */
     int32_t mode;
-    uint64_t min_vars;
+    uint64_t min_vars;      /* 0 and 0.0: the library's policy by cost */
     double ratio;
     int64_t log_iter[16];   /* the first 16 passes: rows out when the pass ran, */
     uint64_t log_vars[16];  /* variants kept by it, */
     double log_ms[16];      /* its time (measuring what was left included) */
+    int64_t view_passes;    /* the passes among `compactions` that read the view before them, not the chunk */
+    int64_t view_refused;   /* times a view's other block did not fit half of the free HBM: the chunk kept its view */
+    uint64_t stream_bytes;  /* the library's own policy: bytes per iteration below which a view is left alone, */
+    double pass_cost;       /* and what a pass byte costs in scoring bytes */
+    int32_t log_src[16];    /* the first 16 passes: 0 = read the chunk, 1 = read a view */
 } utm_compaction_stats;
 int utm_get_compaction_stats(utm_ctx *ctx, utm_compaction_stats *out);
 /* Switch per-launch HIP-event timing of the scoring kernels on/off (same as UTM_FLAG_PROFILE_EVENTS). */

@@ -45,7 +45,9 @@ class CompactionStats(ctypes.Structure):
     _fields_ = [("compactions", ctypes.c_int64), ("working_vars", ctypes.c_uint64), ("pass_bytes", ctypes.c_int64),
                 ("pass_ms", ctypes.c_double), ("refused", ctypes.c_int32), ("mode", ctypes.c_int32),
                 ("min_vars", ctypes.c_uint64), ("ratio", ctypes.c_double),
-                ("log_iter", ctypes.c_int64 * 16), ("log_vars", ctypes.c_uint64 * 16), ("log_ms", ctypes.c_double * 16)]
+                ("log_iter", ctypes.c_int64 * 16), ("log_vars", ctypes.c_uint64 * 16), ("log_ms", ctypes.c_double * 16),
+                ("view_passes", ctypes.c_int64), ("view_refused", ctypes.c_int64), ("stream_bytes", ctypes.c_uint64),
+                ("pass_cost", ctypes.c_double), ("log_src", ctypes.c_int32 * 16)]
 
 
 EXCHANGE_NAMES = {0: "none", 1: "mailboxes", 2: "rccl", 3: "caller-driven", 4: "rccl-allreduce"}

@@ -105,14 +105,15 @@ __global__ __launch_bounds__(UTM_FILTER_SCAN_THREADS) void k_filter_prefix(const
     if (tid == 0) prefix[n_words] = carry;
 }
 
-// cols[c * wp + w] -> out[c * wp_out + ...] for the columns [blockIdx.y * cols_per_group, + cols_per_group) and the input
-// tile blockIdx.x.  w_in = the words of keep[] (bits at or above n_var are clear), prefix[w_in + 1] from k_filter_prefix,
-// `out` zero-filled.  Loads: only where a keep word is set, so below w_in <= wp.  Stores: word g of a column only for
-// 64 g < prefix[w_in] <= 64 wp_out.
+// cols[c * wp + w] -> out[c * wp_out + ...] for the columns c = list[j] (list == nullptr: c = j), j in [blockIdx.y *
+// cols_per_group, + cols_per_group) below n_cols, and the input tile blockIdx.x.  A column keeps its index; one that is not
+// listed is neither read nor written (the destination's zero fill stands for it).  w_in = the words of keep[] (bits at or
+// above n_var are clear), prefix[w_in + 1] from k_filter_prefix, `out` zero-filled.  Loads: only where a keep word is set,
+// so below w_in <= wp.  Stores: word g of a column only for 64 g < prefix[w_in] <= 64 wp_out.
 template <bool NT>
 __global__ __launch_bounds__(256) void k_filter_compact(const u64 *__restrict__ cols, u64 wp, u64 w_in, const u64 *__restrict__ keep,
                                                         const u64 *__restrict__ prefix, u64 *__restrict__ out, u64 wp_out, unsigned n_cols,
-                                                        unsigned cols_per_group)
+                                                        unsigned cols_per_group, const unsigned *__restrict__ list)
 {
     constexpr int U = UTM_FILTER_U;
     __shared__ u64 image[4][U][UTM_FILTER_LDS_WORDS];
@@ -140,10 +141,12 @@ __global__ __launch_bounds__(256) void k_filter_compact(const u64 *__restrict__ 
     const u64 stride = wp / 2;  // a column, in 16-byte units
     for (unsigned c = c_begin; c < c_end; c += U) {  // (uniform over the workgroup)
         v2q x[U];
+        unsigned col[U];  // (uniform: the columns of this round)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+            col[u] = c + u < c_end ? (list ? list[c + u] : c + u) : 0u;
             x[u] = v2q{0, 0};
-            if (mine && c + u < c_end) x[u] = NT ? __builtin_nontemporal_load(src + (u64)(c + u) * stride) : src[(u64)(c + u) * stride];
+            if (mine && c + u < c_end) x[u] = NT ? __builtin_nontemporal_load(src + (u64)col[u] * stride) : src[(u64)col[u] * stride];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(256) void k_filter_compact(const u64 *__restrict__ 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (c + u >= c_end) break;  // (uniform)
-            u64 *dst = out + (u64)(c + u) * wp_out + word0;
+            u64 *dst = out + (u64)col[u] * wp_out + word0;
             for (unsigned k = lane; k < n_out; k += 64) {
                 const u64 v = image[wave][u][k];
                 image[wave][u][k] = 0;
@@ -186,6 +189,20 @@ __global__ __launch_bounds__(256) void k_compact_keep(const u64 *__restrict__ co
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (u64)gridDim.x * 256) {
         u64 k = ~covered[i];
+        if (i == n_words - 1 && (n_var & 63)) k &= (1ull << (n_var & 63)) - 1;
+        keep[i] = k;
+    }
+}
+
+// The same from a working view: what neither the view's mask nor the pending winner's column in the view covers (the
+// view's mask lacks the pending winner until the next scoring launch applies it).  An eligible context is the only
+// shard, so the pending column, if there is one, is a column of `cols`.
+__global__ __launch_bounds__(256) void k_view_keep(const u64 *__restrict__ covered, const u64 *__restrict__ cols, u64 wp, const Pending pend,
+                                                   const IterState *__restrict__ st, u64 n_words, u64 n_var, u64 *__restrict__ keep)
+{
+    const u64 *wcol = pending_column(st, cols, wp, pend);
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (u64)gridDim.x * 256) {
+        u64 k = ~(covered[i] | (wcol ? wcol[i] : 0ull));
         if (i == n_words - 1 && (n_var & 63)) k &= (1ull << (n_var & 63)) - 1;
         keep[i] = k;
     }

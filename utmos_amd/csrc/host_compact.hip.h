@@ -7,8 +7,10 @@
 // new_count are the same bit for bit: a sample's uncovered carriers are the same set, only renumbered, and the samples
 // keep their column index.  The chunk's columns and its full-size covered mask stay where they are for everything else;
 // while a view is valid the scoring launches update the view's mask only, and k_or_rows brings the chunk's mask up to
-// date from the result rows before a compaction and before utm_run returns.  A copy is always made from the chunk's own
-// columns: one destination buffer per chunk, no chain of coordinate maps.
+// date from the result rows before utm_run returns.  The first copy of a run is made from the chunk's columns, every later
+// one from the view before it (two column blocks per chunk, used in turn): nothing outside the loop reads view
+// coordinates, so there is no coordinate map to chain.  A pass moves the columns of the samples that are still selectable;
+// the zero fill stands for the others, whose columns no scoring launch reads from a view.
 #pragma once
 
 // What the integer scoring launches read for a chunk: its working view while that is valid, else the chunk itself.
@@ -44,29 +46,34 @@ static bool compact_eligible(const utm_ctx *c)
            c->n_local == c->n_total && !c->comm && !c->p2p && !c->remote_winner_test;
 }
 
-// k_filter_compact over every local column: about 16k workgroups, tiles x column groups, a group at least 8 columns so
-// that a lane's masks are worth deriving.  `out` is zero-filled, prefix[w_in] <= 64 wp_out.
-static int launch_filter_compact(utm_ctx *c, const u64 *cols, u64 wp, u64 w_in, const u64 *keep, const u64 *prefix, u64 *out, u64 wp_out)
+// k_filter_compact over every local column, or over the n_list columns of `list` (device memory): about 16k workgroups,
+// tiles x column groups, a group at least 8 columns so that a lane's masks are worth deriving.  `out` is zero-filled,
+// prefix[w_in] <= 64 wp_out.
+static int launch_filter_compact(utm_ctx *c, const u64 *cols, u64 wp, u64 w_in, const u64 *keep, const u64 *prefix, u64 *out, u64 wp_out,
+                                 const unsigned *list = nullptr, unsigned n_list = 0)
 {
+    const unsigned n_cols = list ? n_list : c->n_local;
+    if (!n_cols) return UTM_OK;
     const u64 tiles = (wp + UTM_FILTER_TILE_WORDS - 1) / UTM_FILTER_TILE_WORDS;
     if (tiles > 0x7FFFFFFFull) return fail(UTM_EINVAL, "chunk too large for one compaction launch");
     const u64 want_groups = std::max<u64>(1, 16384 / tiles);
-    u64 per_group = std::max<u64>({8, (c->n_local + want_groups - 1) / want_groups, ((u64)c->n_local + 65534) / 65535});
+    u64 per_group = std::max<u64>({8, (n_cols + want_groups - 1) / want_groups, ((u64)n_cols + 65534) / 65535});
     per_group = round_up(per_group, UTM_FILTER_U);
-    const dim3 grid((unsigned)tiles, (unsigned)((c->n_local + per_group - 1) / per_group));
-    const bool nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)c->n_local * wp * 8 > ((u64)c->tune.nt_min_mb << 20);
+    const dim3 grid((unsigned)tiles, (unsigned)((n_cols + per_group - 1) / per_group));
+    const bool nt = c->tune.nt_loads >= 0 ? c->tune.nt_loads != 0 : (u64)n_cols * wp * 8 > ((u64)c->tune.nt_min_mb << 20);
     if (nt)
-        hipLaunchKernelGGL((k_filter_compact<true>), grid, dim3(256), 0, c->stream, cols, wp, w_in, keep, prefix, out, wp_out, c->n_local,
-                           (unsigned)per_group);
+        hipLaunchKernelGGL((k_filter_compact<true>), grid, dim3(256), 0, c->stream, cols, wp, w_in, keep, prefix, out, wp_out, n_cols,
+                           (unsigned)per_group, list);
     else
-        hipLaunchKernelGGL((k_filter_compact<false>), grid, dim3(256), 0, c->stream, cols, wp, w_in, keep, prefix, out, wp_out, c->n_local,
-                           (unsigned)per_group);
+        hipLaunchKernelGGL((k_filter_compact<false>), grid, dim3(256), 0, c->stream, cols, wp, w_in, keep, prefix, out, wp_out, n_cols,
+                           (unsigned)per_group, list);
     HIP_TRY(hipGetLastError());
     return UTM_OK;
 }
 
 // The chunk's own covered mask as of `iter` result rows.  Without a view the scoring launches have kept it up to date but
-// for the pending winner; with one, the winners of rows [r0, iter) are missing (the pending one among them).
+// for the pending winner; with one, the winners of rows [r0, iter) are missing (the pending one among them): one launch
+// over all of them, however many views the chunk has had since.
 static int flush_chunk_covered(utm_ctx *c, Chunk &ch)
 {
     const unsigned blocks = (unsigned)std::min<u64>(1024, (ch.wp + 255) / 256);
@@ -100,85 +107,110 @@ static int flush_views(utm_ctx *c)
     return UTM_OK;
 }
 
-// The small buffers of a pass: keep words, their prefix counts, the view's covered mask (a view is never longer than its chunk).
-static int reserve_view_masks(Chunk &ch)
+// The small buffers of a pass: keep words, their prefix counts, the view's covered mask (a view is never longer than its
+// chunk), the pass's copy of act[].
+static int reserve_view_masks(utm_ctx *c, Chunk &ch)
 {
     WorkView &v = ch.work;
     if (!v.keep) HIP_TRY(hipMalloc(&v.keep, ch.wp * 8));
     if (!v.prefix) HIP_TRY(hipMalloc(&v.prefix, (ch.wp + 1) * 8));
     if (!v.covered) HIP_TRY(hipMalloc(&v.covered, ch.wp * 8));
+    if (!v.list) HIP_TRY(hipMalloc(&v.list, ((size_t)c->n_local + 1) * 4));
     return UTM_OK;
 }
 
-// The view's column block for a copy of wp_out words per column, or *ok = false: no room (the context then never compacts).
-static int reserve_view(utm_ctx *c, Chunk &ch, u64 wp_out, bool *ok)
+// Column block `b` of the view for a copy of wp_out words per column, or *ok = false: no room.  (Never the block a valid
+// view lives in: the first pass of a run has none, a later one asks for the other block.)
+static int reserve_view(utm_ctx *c, Chunk &ch, int b, u64 wp_out, bool *ok)
 {
     WorkView &v = ch.work;
     *ok = false;
     const u64 need = compact_capacity_words(c->n_local, wp_out);
     if (!need) return UTM_OK;
-    if (v.cap_words < need) {
-        (void)hipFree(v.cols);
-        v.cols = nullptr;
-        v.cap_words = 0;
+    if (v.cap_words[b] < need) {
+        (void)hipFree(v.blk[b]);
+        v.blk[b] = nullptr;
+        v.cap_words[b] = 0;
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         const size_t bytes = (size_t)need * 8 + UTM_COLS_SLACK_BYTES;
         if (bytes > free_b / 2) return UTM_OK;
-        if (hipMalloc(&v.cols, bytes) != hipSuccess) {
+        if (hipMalloc(&v.blk[b], bytes) != hipSuccess) {
             (void)hipGetLastError();
-            v.cols = nullptr;
+            v.blk[b] = nullptr;
             return UTM_OK;
         }
-        v.cap_words = need;
+        v.cap_words[b] = need;
     }
     *ok = true;
     return UTM_OK;
 }
 
-// One chunk at a batch boundary (the device is idle, `iter` rows are out): measure what is left of it and, if the policy
-// says so, make the view anew from the chunk's columns.
-static int compact_chunk(utm_ctx *c, Chunk &ch)
+// (`left`: the iterations the running utm_run call still wants)
+static CompactDecision chunk_policy(const utm_ctx *c, const Chunk &ch, u64 uncovered, i64 left)
+{
+    const ScoreView sv = score_view(ch);
+    return compact_policy(sv.n_var, uncovered, c->compact_min_vars, c->compact_ratio, c->iter, c->active_ub, sv.wp, left);
+}
+
+// One chunk at a batch boundary (the device is idle, `iter` rows are out): measure what is left of what the loop scores
+// and, if the policy says so, make the view anew -- from the chunk's columns when it has no view, else from the view.
+static int compact_chunk(utm_ctx *c, Chunk &ch, i64 left)
 {
     WorkView &v = ch.work;
+    const bool from_view = v.valid;
+    const ScoreView src = score_view(ch);
     const i64 bytes0 = c->compact_bytes;
     HIP_TRY(hipEventRecord(c->ev_cmp0, c->stream));
-    // the chunk's covered mask with every winner so far, then keep = what it leaves, and the kept count
-    TRY(flush_chunk_covered(c, ch));
-    TRY(reserve_view_masks(ch));
-    hipLaunchKernelGGL(k_compact_keep, dim3((unsigned)std::min<u64>(1024, (ch.w + 255) / 256)), dim3(256), 0, c->stream, (const u64 *)ch.covered, ch.w,
-                       ch.n_var, v.keep);
-    hipLaunchKernelGGL(k_filter_prefix, dim3(1), dim3(UTM_FILTER_SCAN_THREADS), 0, c->stream, (const u64 *)v.keep, ch.w, v.prefix);
+    TRY(reserve_view_masks(c, ch));
+    const unsigned keep_blocks = (unsigned)std::max<u64>(1, std::min<u64>(1024, (src.w + 255) / 256));
+    if (!from_view) {
+        // the chunk's covered mask with the pending winner, then keep = what it leaves
+        TRY(flush_chunk_covered(c, ch));
+        hipLaunchKernelGGL(k_compact_keep, dim3(keep_blocks), dim3(256), 0, c->stream, (const u64 *)ch.covered, ch.w, ch.n_var, v.keep);
+    } else {
+        // keep = what neither the view's mask nor the pending winner's column in the view covers; the chunk's own mask
+        // waits for flush_views
+        hipLaunchKernelGGL(k_view_keep, dim3(keep_blocks), dim3(256), 0, c->stream, (const u64 *)v.covered, (const u64 *)v.cols, v.wp,
+                           pending_of(c, ch, false), (const IterState *)c->d_st, v.w, v.n_var, v.keep);
+    }
+    hipLaunchKernelGGL(k_filter_prefix, dim3(1), dim3(UTM_FILTER_SCAN_THREADS), 0, c->stream, (const u64 *)v.keep, src.w, v.prefix);
     HIP_TRY(hipGetLastError());
     u64 kept = 0;
-    HIP_TRY(copy_sync(c, &kept, v.prefix + ch.w, 8, hipMemcpyDeviceToHost));
-    c->compact_bytes += (i64)(ch.w * 8 * 4 + 8);  // covered read, keep written and read, prefix written
+    HIP_TRY(copy_sync(c, &kept, v.prefix + src.w, 8, hipMemcpyDeviceToHost));
+    c->compact_bytes += (i64)(src.w * 8 * (from_view ? 5 : 4) + 8);  // covered (and the pending column) read, keep written and read, prefix written
     v.known_uncov = kept;
     v.known_tot = c->captured_seen;
-    const u64 v_work = score_view(ch).n_var;
     bool done = false;
-    if (kept <= ch.n_var && compact_policy(v_work, kept, c->compact_min_vars, c->compact_ratio, c->iter).compact) {
+    if (kept <= src.n_var && chunk_policy(c, ch, kept, left).compact) {
         const u64 wp_out = compact_wp(kept);
+        const int dst = from_view ? 1 - v.cur : 0;
         bool ok = false;
-        TRY(reserve_view(c, ch, wp_out, &ok));
-        if (!ok) {
+        TRY(reserve_view(c, ch, dst, wp_out, &ok));
+        if (!ok && from_view) {
+            v.stuck = true;  // the chunk keeps the view it has
+            c->view_refused += 1;
+        } else if (!ok) {
             c->compact_refused = true;
         } else {
             const size_t bytes = (size_t)c->n_local * wp_out * 8 + UTM_COLS_SLACK_BYTES;
-            if (v.valid) {
-                // the launches of the old view are done (the host is synchronised); the chunk's mask holds what they found
-                v.valid = false;
-            }
-            HIP_TRY(hipMemsetAsync(v.cols, 0, bytes, c->stream));
-            HIP_TRY(hipMemsetAsync(v.covered, 0, wp_out * 8, c->stream));
-            if (kept) TRY(launch_filter_compact(c, ch.cols, ch.wp, ch.w, v.keep, v.prefix, v.cols, wp_out));
+            // the columns to move: act[] as the last launch left it (the host is synchronised; every selectable sample is
+            // in its first active_ub entries, the pending winner has left it), in a buffer of the pass's own
+            const unsigned n_list = std::min(c->active_ub, c->n_local);
+            if (n_list) HIP_TRY(hipMemcpyAsync(v.list, c->d_act, (size_t)n_list * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(v.blk[dst], 0, bytes, c->stream));
+            if (kept) TRY(launch_filter_compact(c, src.cols, src.wp, src.w, v.keep, v.prefix, v.blk[dst], wp_out, v.list, n_list));
+            HIP_TRY(hipMemsetAsync(v.covered, 0, wp_out * 8, c->stream));  // (behind the keep kernel that read it)
+            v.cols = v.blk[dst];
+            v.cur = dst;
             v.n_var = kept;
             v.w = (kept + 63) / 64;
             v.wp = wp_out;
-            v.r0 = c->iter;
+            if (!from_view) v.r0 = c->iter;
             v.valid = true;
-            // keep and prefix read by the lanes, the columns in, the zero fill and the kept words out
-            c->compact_bytes += (i64)(ch.w * 8 * 2 + (u64)c->n_local * ch.w * 8 + bytes + (u64)c->n_local * v.w * 8 + wp_out * 8);
+            // the list copied and read, keep and prefix read by the lanes, the listed columns in, the zero fill and the
+            // kept words out, the view's mask cleared
+            c->compact_bytes += (i64)((u64)n_list * 12 + src.w * 8 * 2 + (u64)n_list * src.w * 8 + bytes + (u64)n_list * v.w * 8 + wp_out * 8);
             done = true;
         }
     }
@@ -195,25 +227,29 @@ static int compact_chunk(utm_ctx *c, Chunk &ch)
             c->compact_pass_iter[k] = c->iter;
             c->compact_pass_vars[k] = kept;
             c->compact_pass_ms[k] = ms;
+            c->compact_pass_src[k] = from_view ? 1 : 0;
         }
         c->compactions += 1;
+        if (from_view) c->view_passes += 1;
     }
     return UTM_OK;
 }
 
 // Every chunk at a batch boundary; *batch = the longest batch the chunks' policies allow next.  A chunk is measured only
-// when it may have reached its threshold: since its last measurement it cannot have lost more variants than the whole
-// matrix has captured (exact for one chunk).
-static int compact_at_boundary(utm_ctx *c, int *batch)
+// when it may pass its rule: since its last measurement it cannot have lost more variants than the whole matrix has
+// captured (exact for one chunk), and both rules -- the caller's share and the library's saving rule -- only get easier
+// to pass as `uncovered` falls, so the lower bound decides.
+static int compact_at_boundary(utm_ctx *c, int *batch, i64 left)
 {
     *batch = UTM_COMPACT_BATCH;
     for (auto &ch : c->chunks) {
         if (c->compact_refused) break;
-        const u64 v_work = score_view(ch).n_var;
+        if (ch.work.stuck) continue;
         const u64 gone = (u64)std::max<i64>(0, c->captured_seen - ch.work.known_tot);
         const u64 at_least = ch.work.known_uncov > gone ? ch.work.known_uncov - gone : 0;
-        if (compact_policy(v_work, at_least, c->compact_min_vars, c->compact_ratio, c->iter).compact) TRY(compact_chunk(c, ch));
-        *batch = std::min(*batch, compact_policy(score_view(ch).n_var, ch.work.known_uncov, c->compact_min_vars, c->compact_ratio, c->iter).batch);
+        if (chunk_policy(c, ch, at_least, left).compact) TRY(compact_chunk(c, ch, left));
+        if (ch.work.stuck) continue;
+        *batch = std::min(*batch, chunk_policy(c, ch, ch.work.known_uncov, left).batch);
     }
     return UTM_OK;
 }
@@ -226,8 +262,10 @@ extern "C" int utm_set_compaction(utm_ctx *c, int32_t mode, uint64_t min_vars, d
     HIP_TRY(hipStreamSynchronize(c->stream));
     invalidate_views(c);  // (the chunks' masks are current: utm_run left them so)
     c->compact_on = mode == 1;
-    c->compact_min_vars = min_vars ? min_vars : UTM_COMPACT_MIN_VARS;
-    c->compact_ratio = ratio > 0 ? ratio : UTM_COMPACT_RATIO;
+    // (both left at 0: the library's policy by cost; one of them given: the other takes its explicit-form default)
+    const bool by_cost = !min_vars && !(ratio > 0);
+    c->compact_min_vars = by_cost ? 0 : min_vars ? min_vars : UTM_COMPACT_MIN_VARS;
+    c->compact_ratio = by_cost ? 0.0 : ratio > 0 ? ratio : UTM_COMPACT_RATIO;
     return UTM_OK;
 }
 
@@ -245,10 +283,15 @@ extern "C" int utm_get_compaction_stats(utm_ctx *c, utm_compaction_stats *out)
     out->mode = c->compact_on ? 1 : 0;
     out->min_vars = c->compact_min_vars;
     out->ratio = c->compact_ratio;
+    out->view_passes = c->view_passes;
+    out->view_refused = c->view_refused;
+    out->stream_bytes = UTM_COMPACT_STREAM_BYTES;
+    out->pass_cost = UTM_COMPACT_PASS_COST;
     for (int k = 0; k < UTM_COMPACT_LOG && k < c->compactions; ++k) {
         out->log_iter[k] = c->compact_pass_iter[k];
         out->log_vars[k] = c->compact_pass_vars[k];
         out->log_ms[k] = c->compact_pass_ms[k];
+        out->log_src[k] = c->compact_pass_src[k];
     }
     return UTM_OK;
 }

@@ -707,7 +707,7 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
         // the host is synchronised here: chunks that have lost enough variants get a (new) compacted view, and while a
         // chunk may still be compacted the run's first batches are short (compact_policy)
         int view_batch = UTM_COMPACT_BATCH;
-        if (compacting) TRY(compact_at_boundary(c, &view_batch));
+        if (compacting) TRY(compact_at_boundary(c, &view_batch, k_max - enq));
         // AF runs start with short batches: the dense -> sparse kernel switch is taken at a batch boundary
         // ... and so is the switch to decremental iterations
         // (the AF form of the persistent loop needs no host decision inside a batch: 256 iterations per launch, as for integers)

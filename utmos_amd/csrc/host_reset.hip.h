@@ -131,6 +131,7 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
     for (auto &ch : c->chunks) {
         ch.work.known_uncov = ch.n_var;
         ch.work.known_tot = 0;
+        ch.work.stuck = false;
     }
     if (restart) TRY(depth_prepare(c));
     // Samples that start out used cover their variants from the first iteration (select.py:36-39) -- on every
@@ -217,7 +218,7 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
         c->af_table_passes = 0;
         c->score_ms = 0;
         c->algo_bytes = 0;
-        c->compactions = 0;
+        c->compactions = c->view_passes = c->view_refused = 0;
         c->compact_bytes = 0;
         c->compact_ms = 0;
     }

@@ -250,11 +250,17 @@ extern "C" int utm_env_overrides(char *buf, uint64_t cap)
 // out empty.  The integer scoring launches take it instead of the chunk while `valid`; everything else keeps reading the
 // chunk.  The buffers outlive utm_reset (the next run compacts into them again) and go with the context.
 struct WorkView {
-    u64 *cols = nullptr, *covered = nullptr;
+    u64 *cols = nullptr, *covered = nullptr;  // cols = blk[cur] while valid
     u64 n_var = 0, w = 0, wp = 0;
-    u64 cap_words = 0;        // room of `cols`, in words (+ UTM_COLS_SLACK_BYTES behind them)
+    // Two column blocks, used in turn: the first pass of a run reads the chunk and writes blk[0], every later one reads
+    // the view in blk[cur] and writes the other block.  cap = room in words (+ UTM_COLS_SLACK_BYTES behind them).
+    u64 *blk[2] = {nullptr, nullptr};
+    u64 cap_words[2] = {0, 0};
+    int cur = 0;
     bool valid = false;
+    bool stuck = false;       // the other block did not fit half of the free HBM: this run keeps the view it has
     u64 *keep = nullptr, *prefix = nullptr;  // the pass's keep words (chunk wp) and their prefix counts (chunk wp + 1)
+    unsigned *list = nullptr;  // the pass's own copy of act[]: the columns it moves (n_local entries)
     i64 r0 = 0;               // while valid: the winners of result rows below r0 are in the chunk's own covered mask
     u64 known_uncov = 0;      // the chunk's uncovered variants when `tot` was known_tot (n_var at a reset: an upper bound)
     i64 known_tot = 0;
@@ -424,10 +430,13 @@ struct utm_ctx {
 
     // working views of the integer loop (host_compact.hip.h)
     bool compact_on = true;
-    u64 compact_min_vars = UTM_COMPACT_MIN_VARS;
-    double compact_ratio = UTM_COMPACT_RATIO;
+    u64 compact_min_vars = 0;       // 0: the library's policy by cost (compact_policy.h), else the caller's threshold
+    double compact_ratio = 0.0;     // ... and share (utm_set_compaction)
     bool compact_refused = false;   // the copy did not fit half of the free HBM: this context never compacts
     i64 compactions = 0;            // since the last utm_reset, as the other statistics
+    i64 view_passes = 0;            // ... those that read a view, not the chunk
+    i64 view_refused = 0;           // ... and the times a view's other block did not fit (the chunk kept its view)
+    int compact_pass_src[UTM_COMPACT_LOG] = {0};
     i64 compact_bytes = 0;
     double compact_ms = 0.0;
     i64 compact_pass_iter[UTM_COMPACT_LOG] = {0};
@@ -571,7 +580,8 @@ extern "C" int utm_ctx_destroy(utm_ctx *c)
         (void)hipFree(ch.list_val);
         (void)hipFree(ch.mask);
         (void)hipFree(ch.planes);
-        (void)hipFree(ch.work.cols); (void)hipFree(ch.work.covered); (void)hipFree(ch.work.keep); (void)hipFree(ch.work.prefix);
+        (void)hipFree(ch.work.blk[0]); (void)hipFree(ch.work.blk[1]); (void)hipFree(ch.work.covered); (void)hipFree(ch.work.keep);
+        (void)hipFree(ch.work.prefix); (void)hipFree(ch.work.list);
     }
     if (c->ev_cmp0) (void)hipEventDestroy(c->ev_cmp0);
     if (c->ev_cmp1) (void)hipEventDestroy(c->ev_cmp1);

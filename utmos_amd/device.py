@@ -359,17 +359,19 @@ class DeviceMatrix:
         return out.value
 
     def set_compaction(self, mode=1, min_vars=0, ratio=0.0):
-        """Integer loop: score a compacted copy of the columns once at most `ratio` of a chunk's working variants are
-        uncovered and it has at least `min_vars` of them (0 / <= 0: the defaults, 2^21 and 0.5).  mode 0 = off.  Same rows."""
+        """Integer loop: score a compacted copy of the columns.  Both at 0 (the default): the library compacts by cost, while
+        an iteration still streams more than the caches hold.  Otherwise: once at most `ratio` of a chunk's working variants
+        are uncovered and it has at least `min_vars` of them (the one left at 0: 2^21 / 0.5).  mode 0 = off.  Same rows."""
         nat.check(nat.lib().utm_set_compaction(self._h, int(mode), int(min_vars), float(ratio)))
 
     def compaction_stats(self):
         """{"compactions", "working_vars", "pass_bytes", "pass_ms", "refused", ...} since the last reset; "passes" lists
-        (rows out, variants kept, ms) of the first 16 compactions."""
+        (rows out, variants kept, ms) of the first 16 compactions and "sources" what each read ("chunk" or "view")."""
         st = nat.CompactionStats()
         nat.check(nat.lib().utm_get_compaction_stats(self._h, ctypes.byref(st)))
         out = {name: getattr(st, name) for name, _ in nat.CompactionStats._fields_ if not name.startswith("log_")}
         out["passes"] = [(st.log_iter[k], st.log_vars[k], st.log_ms[k]) for k in range(min(16, st.compactions))]
+        out["sources"] = ["view" if st.log_src[k] else "chunk" for k in range(min(16, st.compactions))]
         return out
 
     def set_profile(self, on):
