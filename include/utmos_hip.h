@@ -521,6 +521,38 @@ typedef struct utm_compaction_stats {
     int32_t log_src[16];    /* the first 16 passes: 0 = read the chunk, 1 = read a view */
 } utm_compaction_stats;
 int utm_get_compaction_stats(utm_ctx *ctx, utm_compaction_stats *out);
+/* ---- list views of the integer loop -------------------------------------------------------------- */
+/* Beside a working view that a compaction pass has just written, the loop may keep every still selectable column as lists
+ * of its set positions (tile-local 32-bit entries in per-tile segments) and score those: an iteration then reads 4 bytes
+ * per carrier instead of one bit per variant -- same rows bit for bit.  A list is built after a pass when
+ * 4 x (the previous winner's gain) x ratio <= 8 x (words per column of the new view) and one iteration of the new view
+ * streams more than min_stream_bytes; once a run has a list, every later pass rebuilds it.  While a list is valid the
+ * loop runs one launch per iteration.  mode 0 = off, 1 = on (the default); min_stream_bytes = 0 and ratio = 0 stand for
+ * the defaults (1 GiB, 2.0), other values are taken as given.  The call drops any list in use (the views stay).  The entry
+ * buffer of a chunk is allocated at its first build within half of the free HBM, kept across utm_reset and freed with
+ * the context; a build that does not fit leaves the chunk on its bitmap view for that run (utm_list_stats.refused). */
+int utm_set_list_mode(utm_ctx *ctx, int32_t mode, uint64_t min_stream_bytes, double ratio);
+/* Test hook: tile_log2 = 13, 16, 18 or 20 fixes the tile of every build (0: the library's rule); max_entries > 0 refuses a
+ * build of more padded entries than that, as if the buffer had not fitted. */
+int utm_set_list_test(utm_ctx *ctx, int32_t tile_log2, uint64_t max_entries);
+typedef struct utm_list_stats {
+    int64_t builds;          /* list builds since the last utm_reset */
+    int64_t refused;         /* builds refused: no room, or more tiles than a count word can count */
+    int64_t build_bytes;     /* HBM bytes of the builds (part of utm_stats.algo_bytes) */
+    double build_ms;         /* ... and their HIP-event time */
+    int32_t mode;
+    int32_t valid;           /* chunks whose list view is valid now */
+    uint64_t min_stream_bytes;
+    double ratio;
+    int64_t log_iter[16];    /* the first 16 builds: rows out when the build ran, */
+    int32_t log_tiles[16];   /* tiles, */
+    int32_t log_t[16];       /* log2 of the tile's positions, */
+    uint64_t log_entries[16];/* entries, */
+    uint64_t log_padded[16]; /* entries with the segments' padding, */
+    double log_ms[16];       /* time */
+    int64_t log_bytes[16];   /* and HBM bytes */
+} utm_list_stats;
+int utm_get_list_stats(utm_ctx *ctx, utm_list_stats *out);
 /* Switch per-launch HIP-event timing of the scoring kernels on/off (same as UTM_FLAG_PROFILE_EVENTS). */
 int utm_set_profile(utm_ctx *ctx, int32_t on);
 

@@ -50,6 +50,15 @@ class CompactionStats(ctypes.Structure):
                 ("pass_cost", ctypes.c_double), ("log_src", ctypes.c_int32 * 16)]
 
 
+class ListStats(ctypes.Structure):
+    _fields_ = [("builds", ctypes.c_int64), ("refused", ctypes.c_int64), ("build_bytes", ctypes.c_int64),
+                ("build_ms", ctypes.c_double), ("mode", ctypes.c_int32), ("valid", ctypes.c_int32),
+                ("min_stream_bytes", ctypes.c_uint64), ("ratio", ctypes.c_double),
+                ("log_iter", ctypes.c_int64 * 16), ("log_tiles", ctypes.c_int32 * 16), ("log_t", ctypes.c_int32 * 16),
+                ("log_entries", ctypes.c_uint64 * 16), ("log_padded", ctypes.c_uint64 * 16), ("log_ms", ctypes.c_double * 16),
+                ("log_bytes", ctypes.c_int64 * 16)]
+
+
 EXCHANGE_NAMES = {0: "none", 1: "mailboxes", 2: "rccl", 3: "caller-driven", 4: "rccl-allreduce"}
 
 
@@ -105,6 +114,9 @@ PROTOTYPES = {
     "utm_set_profile": [_P, _I32],
     "utm_set_compaction": [_P, _I32, _U64, ctypes.c_double],
     "utm_get_compaction_stats": [_P, ctypes.POINTER(CompactionStats)],
+    "utm_set_list_mode": [_P, _I32, _U64, ctypes.c_double],
+    "utm_set_list_test": [_P, _I32, _U64],
+    "utm_get_list_stats": [_P, ctypes.POINTER(ListStats)],
     "utm_stream_calibration": [_P, _I32, ctypes.POINTER(ctypes.c_double)],
     "utm_set_af_exact_scores": [_P, _I32],
     "utm_set_decremental": [_P, _I32, ctypes.c_double],

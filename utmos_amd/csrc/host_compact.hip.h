@@ -239,6 +239,7 @@ static int compact_chunk(utm_ctx *c, Chunk &ch, i64 left)
 // when it may pass its rule: since its last measurement it cannot have lost more variants than the whole matrix has
 // captured (exact for one chunk), and both rules -- the caller's share and the library's saving rule -- only get easier
 // to pass as `uncovered` falls, so the lower bound decides.
+static int list_after_pass(utm_ctx *c, Chunk &ch);  // (host_list.hip.h)
 static int compact_at_boundary(utm_ctx *c, int *batch, i64 left)
 {
     *batch = UTM_COMPACT_BATCH;
@@ -247,7 +248,9 @@ static int compact_at_boundary(utm_ctx *c, int *batch, i64 left)
         if (ch.work.stuck) continue;
         const u64 gone = (u64)std::max<i64>(0, c->captured_seen - ch.work.known_tot);
         const u64 at_least = ch.work.known_uncov > gone ? ch.work.known_uncov - gone : 0;
+        const i64 passes0 = c->compactions;
         if (chunk_policy(c, ch, at_least, left).compact) TRY(compact_chunk(c, ch, left));
+        if (c->compactions != passes0) TRY(list_after_pass(c, ch));  // (a new view: the list of the one before is gone)
         if (ch.work.stuck) continue;
         *batch = std::min(*batch, chunk_policy(c, ch, ch.work.known_uncov, left).batch);
     }

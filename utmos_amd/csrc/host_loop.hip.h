@@ -69,6 +69,34 @@ static void launch_score_int(utm_ctx *c, const LaunchTimer &t, const Chunk &ch, 
 #undef UTM_LAUNCH_K
 }
 
+// One integer scoring launch of a chunk whose list view is valid: tiles x groups of act[] positions (+ the picker).
+static void launch_score_list(utm_ctx *c, const Chunk &ch, unsigned a_ub, const IntLaunch &how)
+{
+    const ListView &lv = ch.lv;
+    const ScoreView v = score_view(ch);
+    const unsigned group = (unsigned)list_group(a_ub, lv.n_tiles);
+    const unsigned n_groups = (a_ub + group - 1) / group;
+    const unsigned blocks = (unsigned)round_up((u64)lv.n_tiles * n_groups, 8);  // XCD-aware map: tile_of_block()
+    const PickArgs pa = pick_args(c);
+    LaunchTimer t(c);
+#define UTM_LAUNCH_LIST_K(T, FUSED)                                                                                                  \
+    UTM_TIMED_LAUNCH(t, (k_score_list<T, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), (const v4u *)lv.entries,             \
+                     (const unsigned *)lv.offs, c->n_local, v.cols, v.covered, v.wp, pending_of(c, ch, true), (const IterState *)c->d_st, \
+                     (const unsigned *)c->d_act, c->d_cnt, group, n_groups, how.by_pos ? 1u : 0u, pa)
+#define UTM_LAUNCH_LIST(T)                          \
+    if (how.fused == 2) UTM_LAUNCH_LIST_K(T, 2);    \
+    else if (how.fused == 1) UTM_LAUNCH_LIST_K(T, 1); \
+    else UTM_LAUNCH_LIST_K(T, 0)
+    switch (lv.t) {
+    case UTM_LIST_T_TEST: UTM_LAUNCH_LIST(UTM_LIST_T_TEST); break;
+    case 16: UTM_LAUNCH_LIST(16); break;
+    case 18: UTM_LAUNCH_LIST(18); break;
+    default: UTM_LAUNCH_LIST(20); break;
+    }
+#undef UTM_LAUNCH_LIST
+#undef UTM_LAUNCH_LIST_K
+}
+
 static void launch_apply_pending(utm_ctx *c)
 {
     for (auto &ch : c->chunks)
@@ -146,6 +174,10 @@ static void launch_score_af_dense(utm_ctx *c, const Chunk &ch, unsigned a_ub, bo
 static void launch_score_streaming(utm_ctx *c, const Chunk &ch, unsigned a_ub, bool delta = false, const IntLaunch &how = IntLaunch(),
                                    bool fold = false)
 {
+    if (c->af_mode == UTM_AF_NONE && ch.lv.valid) {  // (its view's entry lists: host_list.hip.h)
+        launch_score_list(c, ch, a_ub, how);
+        return;
+    }
     const Tune &tn = c->tune;  // (defaults and what each knob is for: g_knobs, utmos_hip.hip)
     const int target_wgs = tn.target_wgs, min_wgs = tn.min_wgs, min_wgs_big = tn.min_wgs_big, force_steps = tn.tile_steps;
     const int nt_env = tn.nt_loads, nt_min_mb = tn.nt_min_mb;
@@ -230,6 +262,7 @@ static LoopShape loop_shape(utm_ctx *c, int af = 0)
         c->n_ranks != 1 || c->n_local != c->n_total || c->comm || c->p2p || c->n_local >= UTM_LOOP_MAX_LOCAL ||
         (tn.persist_max_samples > 0 && c->n_local > (unsigned)tn.persist_max_samples))
         return sh;
+    if (!af && any_list(c)) return sh;  // (the list phase runs one launch per iteration: host_list.hip.h)
     const u64 wp = af ? c->chunks[0].wp : score_view(c->chunks[0]).wp;  // (integer scores: the working view's columns)
     if (tn.persist_max_mb > 0 && (u64)c->n_local * wp * 8 > ((u64)tn.persist_max_mb << 20)) return sh;
     static int cus = 0, occ_all[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};  // resident blocks per CU for the 8 / 16 / 32 / 64 KiB tile, integer / AF / AF-interval form
@@ -819,10 +852,21 @@ extern "C" int utm_run(utm_ctx *c, int64_t k_max, int64_t *idx_out, int64_t *new
             const i64 ran = std::max<i64>(0, passes - (first_is_full ? 1 : 0));
             if (swapped > ran && ((swapped - ran) & 1)) swap_covered(c);
         }
+        // list phase: a pass reads the entries of the samples selectable in it; the batch's winners leave one by one
+        std::vector<i64> list_winners;
+        if (any_list(c) && rows > 0) {
+            list_winners.resize((size_t)rows);
+            HIP_TRY(copy_sync(c, list_winners.data(), c->d_res_idx + before, (size_t)rows * 8, hipMemcpyDeviceToHost));
+        }
         for (i64 j = 0; j < passes; ++j) {
             const u64 drop = rows > 0 ? (u64)(a0 - a1) * (u64)std::min(j, rows) / (u64)rows : 0;
             const int kind = !af_par ? -1 : ((j == 0 && first_is_full) || deep) ? UTM_PASS_AF_FULL : UTM_PASS_AF_DELTA;
             i64 full = iteration_bytes(c, a0 - drop, kind);
+            if (any_list(c)) {
+                full = 0;
+                for (auto &ch : c->chunks) full += ch.lv.valid ? list_iteration_bytes(ch, a0 - drop) : (i64)((a0 - drop + 3) * score_view(ch).w * 8);
+                if (j < rows) list_winner_leaves(c, list_winners[(size_t)j] - (i64)c->first);
+            }
             if (deep && j < rows) full += (i64)(2 * c->depth_planes + 3) * (i64)c->col_words * 8;  // k_depth_apply: column, covered and planes in and out
             c->brute_bytes += any_view(c) ? iteration_bytes(c, a0 - drop, kind, /*brute=*/true) : full;
             if (!decr) c->algo_bytes += full;

@@ -132,6 +132,7 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
         ch.work.known_uncov = ch.n_var;
         ch.work.known_tot = 0;
         ch.work.stuck = false;
+        ch.lv.had = ch.lv.refused = false;
     }
     if (restart) TRY(depth_prepare(c));
     // Samples that start out used cover their variants from the first iteration (select.py:36-39) -- on every
@@ -221,6 +222,9 @@ static int reset_loop_state(utm_ctx *c, const unsigned char *state, bool restart
         c->compactions = c->view_passes = c->view_refused = 0;
         c->compact_bytes = 0;
         c->compact_ms = 0;
+        c->list_builds = c->list_refused = 0;
+        c->list_bytes = 0;
+        c->list_ms = 0;
     }
     c->prepared = true;
     return UTM_OK;

@@ -22,6 +22,7 @@
 
 #include "kernels.hip.h"
 #include "compact_policy.h"
+#include "list_policy.h"
 
 // ---------------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -266,6 +267,22 @@ struct WorkView {
     i64 known_tot = 0;
 };
 
+// A chunk's list view (host_list.hip.h, list.hip.h): the listed columns of the working view as per-tile segments of entries.
+// Valid only beside the generation of the view it was built from; the buffers outlive utm_reset and go with the context.
+struct ListView {
+    bool valid = false;
+    bool had = false;      // this run has had a list view of the chunk: every later compaction pass rebuilds it
+    bool refused = false;  // a build did not fit: the chunk stays on its bitmap view for this run
+    int t = 0;             // tiles of 2^t positions
+    unsigned n_tiles = 0;
+    unsigned *entries = nullptr;  // quads of u32 entries, all segments back to back
+    u64 cap_quads = 0;
+    unsigned *counts = nullptr, *offs = nullptr;  // [n_tiles x n_local (+ 1)]: set bits per piece, first quad per segment
+    u64 tab_cap = 0;
+    std::vector<unsigned> col_quads;  // per local sample: quads of its segments over all tiles
+    u64 sel_quads = 0;                // ... summed over the samples that are still selectable (byte accounting)
+};
+
 struct Chunk {
     u64 n_var = 0;
     u64 w = 0;   // words holding variants
@@ -289,6 +306,7 @@ struct Chunk {
     u64 *planes = nullptr;         // coverage depth M > 1: bit_length(M) planes of wp words, plane p = bit p of every variant's support
     bool rows_t_valid = false;
     WorkView work;                 // integer scoring: the compacted copy the loop scores while it is valid (host_compact.hip.h)
+    ListView lv;                   // ... and its entry lists, while those are valid (host_list.hip.h)
     std::vector<float> h_af32;
     std::vector<double> h_af64;
 };
@@ -443,13 +461,28 @@ struct utm_ctx {
     u64 compact_pass_vars[UTM_COMPACT_LOG] = {0};
     double compact_pass_ms[UTM_COMPACT_LOG] = {0};
     hipEvent_t ev_cmp0 = nullptr, ev_cmp1 = nullptr;
+
+    // list views of the integer loop (host_list.hip.h)
+    bool list_on = true;
+    u64 list_min_stream = UTM_LIST_MIN_STREAM_BYTES;
+    double list_ratio = UTM_LIST_RATIO;
+    int list_test_t = 0;            // test hook: the tile of every build (0: the rule's)
+    u64 list_test_cap = 0;          // test hook: a build of more padded entries than this is refused (0: no limit)
+    i64 list_builds = 0, list_refused = 0;  // since the last utm_reset
+    i64 list_bytes = 0;
+    double list_ms = 0.0;
+    i64 list_log_iter[UTM_LIST_LOG] = {0};
+    int list_log_tiles[UTM_LIST_LOG] = {0}, list_log_t[UTM_LIST_LOG] = {0};
+    u64 list_log_entries[UTM_LIST_LOG] = {0}, list_log_padded[UTM_LIST_LOG] = {0};
+    double list_log_ms[UTM_LIST_LOG] = {0};
+    i64 list_log_bytes[UTM_LIST_LOG] = {0};
 };
 
 // The loop scores the chunks themselves again; the views' buffers stay.  Only where the chunks' covered masks are current:
 // at an ABI boundary (utm_run brings them up to date before it returns) or where they are rebuilt anyway (utm_reset).
 static void invalidate_views(utm_ctx *c)
 {
-    for (auto &ch : c->chunks) ch.work.valid = false;
+    for (auto &ch : c->chunks) ch.work.valid = ch.lv.valid = false;  // (a list lives in its view's coordinates)
 }
 
 static inline u64 round_up(u64 x, u64 m) { return (x + m - 1) / m * m; }
@@ -582,6 +615,7 @@ extern "C" int utm_ctx_destroy(utm_ctx *c)
         (void)hipFree(ch.planes);
         (void)hipFree(ch.work.blk[0]); (void)hipFree(ch.work.blk[1]); (void)hipFree(ch.work.covered); (void)hipFree(ch.work.keep);
         (void)hipFree(ch.work.prefix); (void)hipFree(ch.work.list);
+        (void)hipFree(ch.lv.entries); (void)hipFree(ch.lv.counts); (void)hipFree(ch.lv.offs);
     }
     if (c->ev_cmp0) (void)hipEventDestroy(c->ev_cmp0);
     if (c->ev_cmp1) (void)hipEventDestroy(c->ev_cmp1);
@@ -676,6 +710,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_depth.hip.h"
 #include "host_reset.hip.h"
 #include "host_compact.hip.h"
+#include "host_list.hip.h"
 #include "host_loop.hip.h"
 #include "host_order.hip.h"
 #include "host_rank.hip.h"

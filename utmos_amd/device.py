@@ -374,6 +374,26 @@ class DeviceMatrix:
         out["sources"] = ["view" if st.log_src[k] else "chunk" for k in range(min(16, st.compactions))]
         return out
 
+    def set_list_mode(self, mode=1, min_stream_bytes=0, ratio=0.0):
+        """Integer loop: beside a freshly compacted view, score per-sample lists of set positions (4 bytes per carrier instead
+        of one bit per variant) once 4 x last gain x `ratio` <= 8 x words per column and an iteration still streams more than
+        `min_stream_bytes`.  Both at 0: the defaults (1 GiB, 2.0).  mode 0 = off.  Same rows."""
+        nat.check(nat.lib().utm_set_list_mode(self._h, int(mode), int(min_stream_bytes), float(ratio)))
+
+    def set_list_test(self, tile_log2=0, max_entries=0):
+        """Test hook: fix the tile of every list build (13, 16, 18, 20; 0 = the rule) / refuse builds above `max_entries`."""
+        nat.check(nat.lib().utm_set_list_test(self._h, int(tile_log2), int(max_entries)))
+
+    def list_stats(self):
+        """{"builds", "refused", "build_bytes", "build_ms", "mode", "valid", ...} since the last reset; "log" lists the
+        first 16 builds as dicts (iter, tiles, t, entries, padded, ms, bytes)."""
+        st = nat.ListStats()
+        nat.check(nat.lib().utm_get_list_stats(self._h, ctypes.byref(st)))
+        out = {name: getattr(st, name) for name, _ in nat.ListStats._fields_ if not name.startswith("log_")}
+        out["log"] = [dict(iter=st.log_iter[k], tiles=st.log_tiles[k], t=st.log_t[k], entries=st.log_entries[k],
+                           padded=st.log_padded[k], ms=st.log_ms[k], bytes=st.log_bytes[k]) for k in range(min(16, st.builds))]
+        return out
+
     def set_profile(self, on):
         nat.check(nat.lib().utm_set_profile(self._h, 1 if on else 0))
 
