@@ -425,6 +425,53 @@ int utm_filter_variants(utm_ctx *ctx, int32_t chunk, const uint64_t *keep, uint6
  * words.  What it replaces: as utm_filter_variants. */
 int utm_filter_columns_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_cols,
                             const uint64_t *keep, uint64_t *out, uint64_t wp_out, uint64_t *n_kept);
+/* ---- replicated selection ------------------------------------------------------------------------ */
+/* n_rep (1..256) greedy selections at once, each over its own subset of the variants and with its own sample states:
+ * replicate b is exactly what utm_set_sample_state(state + b * n_samp_total), utm_reset and utm_run(k) give on the matrix
+ * reduced to the variants of its keep mask (delete-half resampling of the variants, per-class panels, leave-one-out runs).
+ * The columns of a replicate's used samples (state 0) are covered from its start and used samples are never picked;
+ * excluded samples (state 2) are never picked; every row takes the first maximum of popcount(column & live_b), the smallest
+ * sample index among the maxima; a replicate ends silently when its best score is 0, and after the row that captures its
+ * last kept variant.  order_out[b * k + i] = the global sample index of replicate b's row i (-1 after its last row),
+ * new_out[b * k + i] = the variants that row newly captured (0 after the last row), kept_out[b] = the replicate's
+ * variants, n_done[b] = its rows.
+ * keep[chunk][b * W + w], W = ceil(n_var / 64) words of that chunk: the replicate's variants (bits at or above n_var are
+ * ignored).  keep == NULL: hashed masks -- variant v, counted from 0 over all chunks in order, belongs to replicate b iff
+ * (z >> 32) < keep_threshold with z = seed + 0x9E3779B97F4A7C15 * (v + 1) + 0xD1B54A32D192ED03 * (b + 1), z = (z ^ z >> 30)
+ * * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^= z >> 31 (mod 2^64); a threshold of 2^32 keeps
+ * everything.  They are made on the device (k_multi_keep); utm_multi_keep_host is the same function on the host.
+ * Per chunk one k_multi_init launch (live_b = keep_b & valid & ~OR(columns of b's used samples)); per iteration and
+ * chunk k_multi_score, the bit-matrix product of the n_rep live masks with every column (the shape of k_swap_pairs, the
+ * mask rows read from the live buffer), and k_multi_apply (live_b &= ~column of b's winner), with one k_multi_pick in
+ * between.  The k iterations are enqueued without a host round trip per iteration; every launch returns at once when no
+ * replicate is left, and the host looks every 32 iterations.  *pass_ms = the launches' HIP-event time.
+ * Stateless, exactly as utm_swap_gains: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats, the working views and the list views are neither read nor changed.  The
+ * outputs are staged in memory of the call and copied out last.  Rows cleared by an AF of 0 (utm_set_af) have no carriers.
+ * UTM_EINVAL, with the outputs untouched, for n_rep outside 1..256, k < 0, a NULL state or output, a state byte above 2 or
+ * a NULL entry in keep.  UTM_ENOMEM when the n_rep x (words per column) live masks or the n_rep x n_samp_total scores
+ * cannot be had.  UTM_ESTATE on a context that holds only a shard of the samples or has an exchange set up, as
+ * utm_apply_order. */
+int utm_multi_select(utm_ctx *ctx, uint32_t n_rep,
+                     const uint8_t *state,            /* n_rep * n_samp_total: 1 selectable / 0 used / 2 excluded */
+                     const uint64_t *const *keep,     /* n_chunks pointers, each n_rep * ceil(n_var/64) words; NULL: hashed masks */
+                     uint64_t seed, uint64_t keep_threshold,   /* used when keep == NULL */
+                     int64_t k,
+                     int32_t *order_out,              /* n_rep * k global sample indices, -1 after a replicate's last row */
+                     int64_t *new_out,                /* n_rep * k, 0 after the last row */
+                     int64_t *kept_out,               /* n_rep: variants of the replicate (kept bits below n_var, all chunks) */
+                     int64_t *n_done,                 /* n_rep: rows written */
+                     double *pass_ms);                /* may be NULL */
+/* The kernels' arithmetic built for the CPU, replicate by replicate: cols[s * wp + w] of ONE chunk holding n_var <= 64 * wp
+ * variants of n_samp samples (padding bits zero), state[n_rep * n_samp], keep[n_rep * ceil(n_var/64)]; the outputs as
+ * above.  Needs no GPU. */
+int utm_multi_select_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp, uint32_t n_rep,
+                          const uint8_t *state, const uint64_t *keep, int64_t k,
+                          int32_t *order_out, int64_t *new_out, int64_t *kept_out, int64_t *n_done);
+/* The hashed mask of replicate `rep` for the n_var variants from global index first_var_global on: ceil(n_var/64) words,
+ * bits at or above n_var zero.  Needs no GPU. */
+int utm_multi_keep_host(uint64_t seed, uint32_t rep, uint64_t first_var_global, uint64_t n_var,
+                        uint64_t keep_threshold, uint64_t *words);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

@@ -720,6 +720,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_groups.hip.h"
 #include "host_classes.hip.h"
 #include "host_filter.hip.h"
+#include "host_multi.hip.h"
 #include "host_shard.hip.h"
 #include "host_batch.hip.h"
 #include "host_vcf.hip.h"

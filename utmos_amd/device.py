@@ -202,6 +202,44 @@ class DeviceMatrix:
                                            ctypes.byref(ms) if pass_ms else None))
         return (gains, unique, new, base.value, ms.value) if pass_ms else (gains, unique, new, base.value)
 
+    def multi_select(self, k, states, keep=None, seed=0, fraction=None, n_rep=None, pass_ms=False):
+        """B greedy selections at once (utm_multi_select): replicate b runs over its own subset of the variants with its
+        own sample states.  states: uint8 (B, n_samples), or (n_samples,) for every replicate alike (then n_rep says how
+        many; default 1).  keep: a list with one boolean array (B, chunk_vars[chunk]) per chunk, or None for the hashed
+        masks of `seed` that keep a share `fraction` of the variants (stability.keep_threshold; None = 1.0).  Returns
+        (order int32 (B, k), -1 after a replicate's last row; new int64 (B, k); kept int64 (B,); n_done int64 (B,)), with
+        pass_ms the HIP-event time of the launches as a fifth item.  Stateless: nothing of the selection is read or changed."""
+        from .stability import keep_threshold
+        k = int(k)
+        states = np.ascontiguousarray(states, dtype=np.uint8)
+        if states.ndim == 1:
+            states = np.ascontiguousarray(np.broadcast_to(states, (1 if n_rep is None else int(n_rep), states.shape[0])))
+        if states.ndim != 2 or states.shape[1] != self.n_samples or (n_rep is not None and states.shape[0] != int(n_rep)):
+            raise ValueError(f"states must be (n_rep, {self.n_samples})")
+        reps = states.shape[0]
+        words, table = [], None
+        if keep is not None:
+            if len(keep) != len(self.chunk_vars):
+                raise ValueError(f"keep needs one array per chunk ({len(self.chunk_vars)})")
+            for n_var, mask in zip(self.chunk_vars, keep):
+                mask = np.asarray(mask)
+                if mask.dtype != np.bool_ or mask.shape != (reps, n_var):
+                    raise ValueError(f"a keep mask must be a boolean array of shape ({reps}, {n_var})")
+                packed = np.zeros((reps, max(1, (n_var + 63) // 64)), dtype=np.uint64)
+                bits = np.packbits(mask, axis=1, bitorder="little")
+                packed.view(np.uint8)[:, :bits.shape[1]] = bits
+                words.append(packed)
+            table = (ctypes.c_void_p * max(1, len(words)))(*[w.ctypes.data for w in words])
+        order = np.full((reps, max(k, 0)), -1, dtype=np.int32)
+        new = np.zeros((reps, max(k, 0)), dtype=np.int64)
+        kept = np.zeros(reps, dtype=np.int64)
+        done = np.zeros(reps, dtype=np.int64)
+        ms = ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_multi_select(self._h, reps, _ptr(states), table, int(seed) & (2 ** 64 - 1),
+                                             keep_threshold(1.0 if fraction is None else fraction), k, _ptr(order), _ptr(new),
+                                             _ptr(kept), _ptr(done), ctypes.byref(ms) if pass_ms else None))
+        return (order, new, kept, done, ms.value) if pass_ms else (order, new, kept, done)
+
     def pair_counts(self, indices, given=(), tile_groups=0, pass_ms=False):
         """int64 (n, n): shared[i, j] = the variants the samples indices[i] and indices[j] (global sample indices) both
         carry and no sample of `given` carries; the diagonal is each sample's own count under that mask.  Stateless: the

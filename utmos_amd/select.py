@@ -723,6 +723,18 @@ def _build_parser():
                          help="every variant counts until this many selected samples carry it (1..255); above 1 "
                               "new_count / tot_captured count units of min(support, depth) and a column at_depth is "
                               "added [%(default)s]")
+    stability = parser.add_argument_group("Stability Arguments")
+    stability.add_argument("--replicates", type=int, default=None, metavar="B",
+                           help="also run the greedy selection on B (1..256) random subsets of the variants, all at once, "
+                                "with the run's count and --subset / --exclude (masks seeded by --seed)")
+    stability.add_argument("--subsample", type=float, default=None, metavar="F",
+                           help="with --replicates: the share of the variants every replicate keeps, 0 < F <= 1 [0.5]")
+    stability.add_argument("--replicates-out", type=str, default=None, metavar="FILE.npz",
+                           help="with --replicates: write every replicate's rows (order, new, kept, n_done), the band of the "
+                                "coverage curves (pct_mean, pct_min, pct_max), samples, panel, seed and fraction (numpy .npz)")
+    stability.add_argument("--stability-out", type=str, default=None, metavar="FILE.tsv",
+                           help="with --replicates: write, per sample that a replicate or the run selected, in how many "
+                                "replicates (selected, frequency), at which mean row (mean_rank) and whether the run did (in_panel)")
     from . import variant_filter
     variant_filter.add_arguments(parser)
     memory = parser.add_argument_group("Memory Arguments")
@@ -776,6 +788,26 @@ def parse_args(args):
     if args.groups and (args.depth > 1 or args.refine):   # open: DESIGN.md section 15
         logging.error("--groups cannot be combined with %s", "--depth above 1" if args.depth > 1 else "--refine")
         sys.exit(1)
+    if args.replicates is None:
+        given = ("--replicates-out" if args.replicates_out else "--stability-out" if args.stability_out else
+                 "--subsample" if args.subsample is not None else None)
+        if given:
+            logging.error("%s needs --replicates", given)
+            sys.exit(1)
+    else:                                        # the replicates restate the plain greedy run over fewer variants
+        from .stability import MAX_REPLICATES
+        if not 1 <= args.replicates <= MAX_REPLICATES:
+            logging.error("--replicates must be between 1 and %d", MAX_REPLICATES)
+            sys.exit(1)
+        if args.subsample is not None and not 0.0 < args.subsample <= 1.0:
+            logging.error("--subsample must be above 0 and at most 1")
+            sys.exit(1)
+        clash = ("--af" if args.af else "--weights" if args.weights else "--depth above 1" if args.depth > 1 else
+                 f"--mode {args.mode}" if args.mode != "greedy" else "--refine" if args.refine else
+                 "--groups" if args.groups else "--include" if args.include else None)
+        if clash:
+            logging.error("--replicates runs the plain greedy selection on subsets of the variants and cannot be combined with %s", clash)
+            sys.exit(1)
     if (args.samples_out or args.represent_out) and args.count >= 1 and int(args.count) > MAX_PANEL:
         logging.error("--samples-out and --represent-out hold a panel of at most %d rows (-c %d asks for more)", MAX_PANEL, int(args.count))
         sys.exit(1)
@@ -793,7 +825,8 @@ def parse_args(args):
                       "Write the store first, or write a filtered one with `filter -o`")
         sys.exit(1)
     options = {name: value for name, value in vars(args).items()
-               if (name not in ("variants_out", "samples_out", "represent_out", "groups", "groups_out", "group_max") + filters or value is not None)
+               if (name not in ("variants_out", "samples_out", "represent_out", "groups", "groups_out", "group_max", "replicates", "subsample",
+                                "replicates_out", "stability_out") + filters or value is not None)
                and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
@@ -845,6 +878,24 @@ def write_variants(path, data, selected, depth, in_files, ranks=None):
     logging.info("%s: capture ranks of %d variants under %d selected samples", path, len(arrays["rank"]), len(selected))
 
 
+def refuse_af_store(args):
+    """--replicates on a store made with --af: refused from the store's header, before anything is loaded."""
+    if args.lowmem != 1 or not os.path.exists(args.in_files[0]):
+        return
+    try:
+        if args.in_files[0].endswith(H5_SUFFIX):
+            from .h5store import H5Store
+            has_af = H5Store(args.in_files[0]).data.kind == "float"
+        else:
+            has_af = StoreReader(args.in_files[0]).has_af
+    except (OSError, ValueError) as err:
+        logging.error("%s", err)
+        sys.exit(1)
+    if has_af:
+        logging.error("--replicates counts variants and cannot run on a store made with --af: recreate it without --af")
+        sys.exit(1)
+
+
 def select_main(cmdargs):
     """`utmos select`: load, select, write the TSV (header + one flushed line per selected sample, select.py:440-446)."""
     global MAXMEM
@@ -869,6 +920,11 @@ def select_main(cmdargs):
     if args.groups and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         logging.error("--groups needs the whole sample axis on one GPU: run a single process")
         sys.exit(1)
+    if args.replicates is not None:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            logging.error("--replicates needs the whole sample axis on one GPU: run a single process")
+            sys.exit(1)
+        refuse_af_store(args)
     from . import variant_filter
     criteria = variant_filter.Criteria.from_args(args)
     variant_filter.refuse_several_processes(criteria)
@@ -955,6 +1011,17 @@ def select_main(cmdargs):
             write_log(args.refine_out, swaps, [str(name) for name in data["samples"]])
         if args.groups_out:
             groups.write_group_curve(args.groups_out, data, selected, group_of, group_names)
+        if args.replicates is not None:          # stateless on the matrix as loaded (and filtered): the run's count and states
+            from . import stability
+            names = np.asarray(data["samples"]).astype(str)
+            fraction = 0.5 if args.subsample is None else args.subsample
+            result = stability.run_replicates(matrix, resolve_select_count(len(names), args.count), sample_states(names, subset, exclude),
+                                              args.replicates, fraction, args.seed)
+            panel = selected_order(data, selected)
+            if args.replicates_out:
+                stability.write_replicates(args.replicates_out, result, names, panel, args.seed, fraction)
+            if args.stability_out:
+                stability.write_table(args.stability_out, stability.selection_table(result[0], result[3], names, panel))
         ranks = None
         if args.variants_out and per_sample:     # both read the capture ranks of the printed order: one pass per chunk
             order = selected_order(data, selected)
