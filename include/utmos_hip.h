@@ -472,6 +472,49 @@ int utm_multi_select_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uin
  * bits at or above n_var zero.  Needs no GPU. */
 int utm_multi_keep_host(uint64_t seed, uint32_t rep, uint64_t first_var_global, uint64_t n_var,
                         uint64_t keep_threshold, uint64_t *words);
+/* ---- coverage bound ------------------------------------------------------------------------------ */
+/* A certified upper bound on what ANY panel of k of the candidate samples can capture beyond the `given` samples, by
+ * Lagrangian relaxation of maximum coverage.  For multipliers lambda_v in [0, 1] and any k columns S,
+ *     F(S) <= sum_v (1 - lambda_v) + (the k largest column sums s_j = sum_{v in j} lambda_v) = L(lambda),
+ * and `iters` projected subgradient steps on L approach the LP bound.  lambda is 16-bit fixed point, Q = 65,536 = 1.0, so
+ * everything is an integer.  live = the valid variant bits & ~OR(columns of `given`), over all chunks; lambda_v = Q on the
+ * live variants at the start.  For t = 0 .. iters - 1:
+ *   s_j   = sum of lambda_v over the live variants column cand[j] carries (int64, all chunks);
+ *   P_t   = the min(k, n_cand) positions j with the largest s_j, ties to the smaller position in cand;
+ *   L_t   = sum_live (Q - lambda_v) + sum_{j in P_t} s_j                                   -> hist_out[t];
+ *   c_v   = the j in P_t whose column carries v;   eta_t = max(1, step0 >> min(63, t / period));
+ *   lambda_v <- min(Q, max(0, lambda_v - eta_t * (c_v - 1))) for every live v.
+ * *n_live_out = the live variants, *bound_out = min(n_live, min_t floor(L_t / Q)), *best_iter_out = the first t at that
+ * minimum; hist_out[0] / Q is the trivial bound, the k largest live column counts.  lambda_out[chunk][v] = lambda after the
+ * last update, 0 where v is not live.  The call is deterministic: the lambda behind best_iter is what iters = best_iter
+ * returns.  step0 == 0: Q / 4; period == 0: max(1, iters / 14).  cand == NULL with n_cand == 0: every sample, in index order.
+ * Per chunk one k_swap_masks launch (the live mask, as utm_pair_counts) and one k_bound_init; per iteration and chunk
+ * k_bound_sums (every candidate column once, 4-variant nibble tables of lambda in LDS) and k_bound_update (the picked
+ * columns into bit-plane counters, the clamp update, the next constant term), with one single-workgroup k_bound_pick in
+ * between.  All iterations are enqueued at once; the history comes back once at the end.  *pass_ms = their HIP-event time.
+ * Stateless, exactly as utm_swap_gains: it reads the columns and nothing else -- covered, the depth planes, the sample
+ * states, the rows, a pending winner, utm_stats, the working views and the list views are neither read nor changed.  Used
+ * and excluded samples are accepted in both lists; a sample in both has no live variants.  Rows cleared by an AF of 0
+ * (utm_set_af) have no carriers: such a row stays live at lambda = Q and adds nothing.
+ * UTM_EINVAL, with the outputs untouched, for a NULL hist_out, a NULL list with a nonzero length, an index out of range, a
+ * duplicate within either list, k < 1, iters outside 1..65,535, step0 above 65,536 or a NULL entry in lambda_out.
+ * UTM_ENOMEM when the lambda, mask or sum buffers cannot be had.  UTM_ESTATE on a context that holds only a shard of the
+ * samples or has an exchange set up, as utm_apply_order. */
+int utm_coverage_bound(utm_ctx *ctx, const int64_t *cand, int64_t n_cand,   /* NULL / 0: every sample, index order */
+                       const int64_t *given, int64_t n_given,               /* may be NULL / 0 */
+                       int64_t k, int32_t iters, uint32_t step0, uint32_t period,   /* 0: defaults */
+                       int64_t *hist_out      /* iters values L_t */,
+                       int64_t *bound_out, int32_t *best_iter_out, int64_t *n_live_out,   /* each may be NULL */
+                       uint32_t *const *lambda_out /* n_chunks pointers of n_var each, or NULL */,
+                       double *pass_ms /* may be NULL */);
+/* ms_out[3] = the summed HIP-event times of the last utm_coverage_bound's k_bound_sums, k_bound_pick and k_bound_update
+ * launches; zeros unless the context was created with UTM_FLAG_PROFILE_EVENTS. */
+int utm_coverage_bound_times(utm_ctx *ctx, double *ms_out);
+/* The same arithmetic built for the CPU: cols[s * wp + w] of ONE chunk holding n_var <= 64 * wp variants of n_samp samples
+ * (padding bits zero); lambda_out[n_var] or NULL; the other outputs as above.  Needs no GPU. */
+int utm_coverage_bound_host(const uint64_t *cols, uint64_t wp, uint64_t n_var, uint32_t n_samp, const uint32_t *cand, uint64_t n_cand,
+                            const uint32_t *given, uint64_t n_given, int64_t k, int32_t iters, uint32_t step0, uint32_t period,
+                            int64_t *hist_out, int64_t *bound_out, int32_t *best_iter_out, int64_t *n_live_out, uint32_t *lambda_out);
 /* Scores of the NEXT iteration without selecting: counts[n_local] (new variants per local sample,
  * 0 for non-selectable) and final scores[n_local].  Either may be NULL.  Parity/debug aid. */
 int utm_peek_scores(utm_ctx *ctx, int64_t *counts, double *scores);

@@ -105,6 +105,11 @@ PROTOTYPES = {
     "utm_multi_select": [_P, _U32, _P, _P, _U64, _U64, _I64, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_double)],
     "utm_multi_select_host": [_P, _U64, _U64, _U32, _U32, _P, _P, _I64, _P, _P, _P, _P],
     "utm_multi_keep_host": [_U64, _U32, _U64, _U64, _U64, _P],
+    "utm_coverage_bound": [_P, _P, _I64, _P, _I64, _I64, _I32, _U32, _U32, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I32),
+                           ctypes.POINTER(_I64), _P, ctypes.POINTER(ctypes.c_double)],
+    "utm_coverage_bound_times": [_P, _P],
+    "utm_coverage_bound_host": [_P, _U64, _U64, _U32, _P, _U64, _P, _U64, _I64, _I32, _U32, _U32, _P, ctypes.POINTER(_I64),
+                                ctypes.POINTER(_I32), ctypes.POINTER(_I64), _P],
     "utm_set_depth": [_P, _I32],
     "utm_get_depth": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_double)],
     "utm_get_at_depth": [_P, _I64, _I64, _P],

@@ -446,6 +446,8 @@ struct utm_ctx {
     double score_ms = 0.0;
     hipEvent_t ev_loop0 = nullptr, ev_loop1 = nullptr;
 
+    double bound_ms[3] = {0.0, 0.0, 0.0};  // the last utm_coverage_bound's kernel times (UTM_FLAG_PROFILE_EVENTS)
+
     // working views of the integer loop (host_compact.hip.h)
     bool compact_on = true;
     u64 compact_min_vars = 0;       // 0: the library's policy by cost (compact_policy.h), else the caller's threshold
@@ -721,6 +723,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_classes.hip.h"
 #include "host_filter.hip.h"
 #include "host_multi.hip.h"
+#include "host_bound.hip.h"
 #include "host_shard.hip.h"
 #include "host_batch.hip.h"
 #include "host_vcf.hip.h"

@@ -1,5 +1,6 @@
 """HBM-resident bit-packed presence matrix + the device-resident greedy loop (thin object layer
 over the C ABI).  One DeviceMatrix = one GPU = one contiguous shard of the sample axis."""
+import collections
 import ctypes
 
 import numpy as np
@@ -9,6 +10,9 @@ from . import _native as nat
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+BoundResult = collections.namedtuple("BoundResult", "hist bound best_iter n_live pass_ms lambdas")
 
 
 class DeviceMatrix:
@@ -239,6 +243,38 @@ class DeviceMatrix:
                                              keep_threshold(1.0 if fraction is None else fraction), k, _ptr(order), _ptr(new),
                                              _ptr(kept), _ptr(done), ctypes.byref(ms) if pass_ms else None))
         return (order, new, kept, done, ms.value) if pass_ms else (order, new, kept, done)
+
+    def coverage_bound(self, k, cand=None, given=None, iters=200, step0=0, period=0, want_lambda=False):
+        """A certified upper bound on what any `k` of the samples `cand` (global sample indices; None: every sample) can
+        capture beyond the samples `given`, by `iters` projected subgradient steps on the Lagrangian relaxation of maximum
+        coverage (utm_coverage_bound; step0 / period 0: the defaults).  Returns a BoundResult: hist (int64 L_t per
+        iteration, in units of 1/65,536 variant), bound = min(n_live, min_t hist[t] // 65,536), best_iter, n_live (the
+        variants no `given` sample carries), pass_ms (HIP-event time of the launches) and lambdas (want_lambda: one uint32
+        array per chunk, the multipliers after the last step; else None).  Stateless: the columns are read, nothing of the
+        selection is read or changed."""
+        c = None if cand is None else np.ascontiguousarray(cand, dtype=np.int64).reshape(-1)
+        g = None if given is None else np.ascontiguousarray(given, dtype=np.int64).reshape(-1)
+        iters = int(iters)
+        hist = np.zeros(max(iters, 1), dtype=np.int64)
+        lambdas = table = None
+        if want_lambda:
+            lambdas = [np.zeros(max(n_var, 1), dtype=np.uint32) for n_var in self.chunk_vars]
+            table = (ctypes.c_void_p * max(1, len(lambdas)))(*[a.ctypes.data for a in lambdas])
+        bound, best, n_live, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        nat.check(nat.lib().utm_coverage_bound(self._h, _ptr(c) if c is not None and len(c) else None, 0 if c is None else len(c),
+                                               _ptr(g) if g is not None and len(g) else None, 0 if g is None else len(g), int(k), iters,
+                                               int(step0), int(period), _ptr(hist), ctypes.byref(bound), ctypes.byref(best),
+                                               ctypes.byref(n_live), table, ctypes.byref(ms)))
+        if want_lambda:
+            lambdas = [a[:n_var] for a, n_var in zip(lambdas, self.chunk_vars)]
+        return BoundResult(hist[:iters], bound.value, best.value, n_live.value, ms.value, lambdas)
+
+    def coverage_bound_times(self):
+        """(sums, pick, update): the summed HIP-event times in ms of the last coverage_bound call's three kernels; zeros
+        unless the matrix was created with profile_events."""
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().utm_coverage_bound_times(self._h, _ptr(out)))
+        return tuple(out.tolist())
 
     def pair_counts(self, indices, given=(), tile_groups=0, pass_ms=False):
         """int64 (n, n): shared[i, j] = the variants the samples indices[i] and indices[j] (global sample indices) both

@@ -735,6 +735,16 @@ def _build_parser():
     stability.add_argument("--stability-out", type=str, default=None, metavar="FILE.tsv",
                            help="with --replicates: write, per sample that a replicate or the run selected, in how many "
                                 "replicates (selected, frequency), at which mean row (mean_rank) and whether the run did (in_panel)")
+    quality = parser.add_argument_group("Bound Arguments")
+    quality.add_argument("--bound-out", type=str, default=None, metavar="FILE.tsv",
+                         help="also write a certified upper bound on what ANY panel of the same size can capture (k, captured, "
+                              "bound_trivial, bound_online, bound_lagrange, bound, share): the panel captures at least `share` "
+                              "of the best possible one.  --include samples are part of every panel compared with; with "
+                              "--group-max the bound is for the problem without the quota, which is still a bound")
+    quality.add_argument("--bound-iters", type=int, default=None, metavar="T",
+                         help="with --bound-out: subgradient steps of the Lagrangian bound, 1..65535 [200]")
+    quality.add_argument("--bound-at", type=str, default=None, metavar="K[,K...]",
+                         help="with --bound-out: the panel sizes to bound [the number of rows the run produced]")
     from . import variant_filter
     variant_filter.add_arguments(parser)
     memory = parser.add_argument_group("Memory Arguments")
@@ -779,6 +789,8 @@ def parse_args(args):
         if clash:
             logging.error("--refine improves the plain number of captured variants and cannot be combined with %s", clash)
             sys.exit(1)
+    from . import bound
+    bound.refuse(args)
     if (args.groups_out or args.group_max is not None) and not args.groups:
         logging.error("--groups-out and --group-max need --groups")
         sys.exit(1)
@@ -826,7 +838,7 @@ def parse_args(args):
         sys.exit(1)
     options = {name: value for name, value in vars(args).items()
                if (name not in ("variants_out", "samples_out", "represent_out", "groups", "groups_out", "group_max", "replicates", "subsample",
-                                "replicates_out", "stability_out") + filters or value is not None)
+                                "replicates_out", "stability_out", "bound_out", "bound_iters", "bound_at") + filters or value is not None)
                and (name not in ("refine", "refine_out") or value)}
     logging.info("options in effect: %s", json.dumps(options, sort_keys=True))
     return args
@@ -925,7 +937,10 @@ def select_main(cmdargs):
             logging.error("--replicates needs the whole sample axis on one GPU: run a single process")
             sys.exit(1)
         refuse_af_store(args)
-    from . import variant_filter
+    from . import bound, variant_filter
+    bound.refuse_several_processes(args)
+    if args.bound_out:
+        bound.refuse_small_sizes(bound.parse_bound_at(args.bound_at), len(dict.fromkeys(parse_sample_lists(args.include))))
     criteria = variant_filter.Criteria.from_args(args)
     variant_filter.refuse_several_processes(criteria)
     lists = [path for path in (args.keep_variants, args.drop_variants) if path]
@@ -965,6 +980,9 @@ def select_main(cmdargs):
         logging.critical("The store was created with --af and scores by allele frequency: add --af or recreate it")
         if args.refine:
             logging.error("--refine improves the plain number of captured variants and cannot run on a store made with --af")
+            sys.exit(1)
+        if args.bound_out:
+            logging.error("--bound-out bounds the plain number of captured variants and cannot run on a store made with --af")
             sys.exit(1)
 
     transport = None
@@ -1022,6 +1040,11 @@ def select_main(cmdargs):
                 stability.write_replicates(args.replicates_out, result, names, panel, args.seed, fraction)
             if args.stability_out:
                 stability.write_table(args.stability_out, stability.selection_table(result[0], result[3], names, panel))
+        if args.bound_out:                       # stateless on the matrix as loaded (and filtered)
+            names = np.asarray(data["samples"]).astype(str)
+            include = parse_sample_lists(args.include)
+            bound.write_outputs(args.bound_out, data, selected, bound.parse_bound_at(args.bound_at), sample_states(names, subset, exclude),
+                                resolve_include(names, include, exclude) if include else (), args.bound_iters or 200)
         ranks = None
         if args.variants_out and per_sample:     # both read the capture ranks of the printed order: one pass per chunk
             order = selected_order(data, selected)
