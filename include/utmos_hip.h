@@ -643,6 +643,19 @@ typedef struct utm_list_stats {
     int64_t log_bytes[16];   /* and HBM bytes */
 } utm_list_stats;
 int utm_get_list_stats(utm_ctx *ctx, utm_list_stats *out);
+/* The shape of the launches that score a list.  A wave walks one segment with all 64 lanes, or -- for a build whose mean
+ * segment is at most 64 quads of entries -- four segments at once, 16 lanes each; the launches of such a build aim at a
+ * workgroup target of their own.  lanes = 16 or 64 fixes the form of every build from the next one on (a list in use
+ * keeps its form; tiles of 2^18 and 2^20 positions have the 64-lane form only), 0 = the library's rule.  target_wgs =
+ * 1 .. 65536 replaces the target of the 16-lane launches from the next launch on, 0 = the library's.  Anything else is
+ * UTM_EINVAL and changes nothing.  The call drops nothing and the rows are the same bit for bit; the setting outlives
+ * utm_reset. */
+int utm_set_list_shape(utm_ctx *ctx, int32_t lanes, int32_t target_wgs);
+/* For the first 16 builds since the last utm_reset (as utm_list_stats.log_*): lanes[k] = the lanes that share a segment in
+ * the launches of build k, as decided once at the build (64 for a tile without the 16-lane form, whatever was asked);
+ * wgs[k] = the scoring workgroups of its first launch (0: none yet); *n = builds reported.  lanes and wgs hold 16 values
+ * each. */
+int utm_get_list_shape(utm_ctx *ctx, int32_t *lanes, int32_t *wgs, int32_t *n);
 /* Switch per-launch HIP-event timing of the scoring kernels on/off (same as UTM_FLAG_PROFILE_EVENTS). */
 int utm_set_profile(utm_ctx *ctx, int32_t on);
 

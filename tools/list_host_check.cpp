@@ -2,8 +2,9 @@
 // for a sanitizer build; pure host code, no GPU call:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -I utmos_amd/csrc tools/list_host_check.cpp -o list_host_check && ./list_host_check
 // The gate at equality and on either side of the byte floor, the two shapes the suite binds to the bitmap path, the tile
-// rule over every column length up to 2^26 words and at the arrival field's limit, launch shapes that cover every
-// position, and the scan against a plain recount (padding, empty segments, the 32-bit limit).
+// rule over every column length up to 2^26 words and at the arrival field's limit, launch shapes of both forms (whole
+// rounds, every position covered, workgroups within the target, saturation), the lanes rule at its threshold and on the
+// headline shape's six builds, and the scan against a plain recount (padding, empty segments, the 32-bit limit).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -58,14 +59,54 @@ int main()
         CHECK(list_tile_log2(wp, 17, 4095) == t);  // (a size that is not built: the rule's)
     }
     CHECK(list_tiles(128, 13) == 1 && list_tiles(256, 13) == 2 && list_tiles(1024, 16) == 1 && list_tiles(1152, 16) == 2);
-    // launch shapes: groups of whole waves' worth that cover every position
-    for (uint64_t a = 1; a <= 70000; a += (a < 3000 ? 1 : 997))
-        for (uint64_t tiles : {1ull, 2ull, 5ull, 23ull, 48ull, 4095ull}) {
-            const uint64_t g = list_group(a, tiles);
-            CHECK(g >= 4 && g % 4 == 0 && (a + g - 1) / g * g >= a);
-            CHECK((a + g - 1) / g * tiles <= UTM_LIST_TARGET_WGS + tiles || g == 4);
+    // launch shapes: groups of whole rounds (4 positions a round at 64 lanes, 16 at 16) that cover every position and keep
+    // the workgroups within the target plus rounding
+    for (uint64_t round : {4ull, 16ull})
+        for (uint64_t target : {1ull, 64ull, 1024ull, 2048ull, 4096ull, 65536ull})
+            for (uint64_t a = 1; a <= 70000; a += (a < 3000 ? 1 : 997))
+                for (uint64_t tiles : {1ull, 2ull, 5ull, 23ull, 48ull, 4095ull}) {
+                    const uint64_t g = list_group(a, tiles, round, target);
+                    const uint64_t groups = (a + g - 1) / g;
+                    CHECK(g >= round && g % round == 0 && groups * g >= a && (groups - 1) * g < a);
+                    CHECK(groups * tiles <= target + tiles || g == round);
+                }
+    // ... the whole-wave form's as they were: ceil(a x tiles / 1,024) rounded up to 4
+    for (uint64_t a = 1; a <= 3000; ++a)
+        for (uint64_t tiles : {1ull, 14ull, 23ull, 38ull, 48ull}) {
+            uint64_t g = (a * tiles + UTM_LIST_TARGET_WGS - 1) / UTM_LIST_TARGET_WGS;
+            g = (g + 3) / 4 * 4;
+            CHECK(list_group(a, tiles, 4, list_target_wgs(64, 0)) == (g < 4 ? 4 : g));
+            CHECK(list_group(a, tiles, 4, list_target_wgs(64, 4096)) == (g < 4 ? 4 : g));  // (a forced target is the row form's)
         }
-    CHECK(list_group(UINT64_MAX, UINT64_MAX) >= 4);
+    CHECK(list_target_wgs(16, 0) == UTM_LIST_TARGET_WGS_ROWS && list_target_wgs(16, 64) == 64 && list_target_wgs(64, 0) == UTM_LIST_TARGET_WGS);
+    // ... and absurd inputs saturate: no wrap to a small group, no division by zero
+    CHECK(list_group(UINT64_MAX, UINT64_MAX, 4, 1024) >= UINT64_MAX / 1024 && list_group(UINT64_MAX, UINT64_MAX, 4, 1024) % 4 == 0);
+    CHECK(list_group(UINT64_MAX, UINT64_MAX, 16, 1) == UINT64_MAX);  // (saturated)
+    CHECK(list_group(UINT64_MAX, 1, 16, UINT64_MAX) == 16 && list_group(0, 0, 16, 2048) == 16 && list_group(5, 5, 0, 0) == 28);
+    // lanes per segment: the mean segment against one batch of a row, at equality and one past it
+    CHECK(list_lanes(64 * 10, 2, 5) == 16 && list_lanes(64 * 10 + 1, 2, 5) == 64 && list_lanes(0, 2, 5) == 16);
+    CHECK(list_lanes(0, 0, 5) == 64 && list_lanes(7, 3, 0) == 64);  // (no segment at all: the form there has always been)
+    CHECK(list_lanes(UINT64_MAX, UINT64_MAX, UINT64_MAX) == 16 && list_lanes(UINT64_MAX, 1, 1) == 64 && list_lanes(1, UINT64_MAX, UINT64_MAX) == 16);
+    for (uint64_t tiles = 1; tiles <= 48; ++tiles)
+        for (uint64_t listed = 1; listed <= 2504; listed += 9)
+            for (uint64_t mean : {1ull, 63ull, 64ull, 65ull, 1000ull}) {
+                const uint64_t q = mean * tiles * listed;
+                CHECK(list_lanes(q, tiles, listed) == (mean <= UTM_LIST_ROW_QUADS ? 16 : 64));
+                CHECK(list_lanes(q + 1, tiles, listed) == (mean < UTM_LIST_ROW_QUADS ? 16 : 64));
+            }
+    // ... and only the tiles that have the 16-lane form take it
+    for (int t : {0, 13, 14, 16, 18, 20})
+        for (int l : {0, 16, 64, 7}) CHECK(list_lanes_of_tile(t, l) == ((l == 16 && (t == 13 || t == 16)) ? 16 : 64));
+    // the six builds of the headline shape (10M x 2,504, select all: padded entries / 4, tiles, listed columns)
+    {
+        const uint64_t b[6][3] = {{178723988 / 4, 23, 2488}, {62179312 / 4, 18, 2456}, {26677104 / 4, 14, 2392},
+                                  {11939040 / 4, 38, 2264},  {4907380 / 4, 24, 2008},  {2606020 / 4, 16, 1752}};
+        const int want[6] = {64, 64, 64, 16, 16, 16};
+        for (int k = 0; k < 6; ++k) CHECK(list_lanes(b[k][0], b[k][1], b[k][2]) == want[k]);
+        // ... whose 16-lane launches leave a wave 3, 2 and 1 rounds at the default target
+        CHECK(list_group(2264, 38, 16, list_target_wgs(16, 0)) == 48 && list_group(2008, 24, 16, list_target_wgs(16, 0)) == 32 &&
+              list_group(1752, 16, 16, list_target_wgs(16, 0)) == 16);
+    }
     // the scan
     uint64_t seed = 12345;
     for (int round = 0; round < 200; ++round) {

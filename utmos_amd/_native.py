@@ -125,6 +125,8 @@ PROTOTYPES = {
     "utm_set_list_mode": [_P, _I32, _U64, ctypes.c_double],
     "utm_set_list_test": [_P, _I32, _U64],
     "utm_get_list_stats": [_P, ctypes.POINTER(ListStats)],
+    "utm_set_list_shape": [_P, _I32, _I32],
+    "utm_get_list_shape": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
     "utm_stream_calibration": [_P, _I32, ctypes.POINTER(ctypes.c_double)],
     "utm_set_af_exact_scores": [_P, _I32],
     "utm_set_decremental": [_P, _I32, ctypes.c_double],

@@ -101,8 +101,12 @@ static int build_list(utm_ctx *c, Chunk &ch)
     lv.t = t;
     lv.n_tiles = (unsigned)tiles;
     lv.sel_quads = quads;
+    lv.lanes = list_lanes_of_tile(t, c->list_shape_lanes ? c->list_shape_lanes : list_lanes(quads, tiles, n_list));
     const i64 k = c->list_builds;
+    lv.log_slot = k < UTM_LIST_LOG ? (int)k : -1;
     if (k < UTM_LIST_LOG) {
+        c->list_log_lanes[k] = lv.lanes;
+        c->list_log_wgs[k] = 0;  // (its first launch writes it: launch_score_list)
         c->list_log_iter[k] = c->iter;
         c->list_log_tiles[k] = (int)tiles;
         c->list_log_t[k] = t;
@@ -163,6 +167,29 @@ extern "C" int utm_set_list_test(utm_ctx *c, int32_t tile_log2, uint64_t max_ent
         return fail(UTM_EINVAL, "tile_log2 %d: 0 (the rule), %d, 16, 18 or 20", tile_log2, UTM_LIST_T_TEST);
     c->list_test_t = tile_log2;
     c->list_test_cap = max_entries;
+    return UTM_OK;
+}
+
+extern "C" int utm_set_list_shape(utm_ctx *c, int32_t lanes, int32_t target_wgs)
+{
+    CTX(c);
+    if (lanes != 0 && lanes != 16 && lanes != 64) return fail(UTM_EINVAL, "lanes %d: 0 (the rule), 16 or 64", lanes);
+    if (target_wgs < 0 || target_wgs > UTM_LIST_TARGET_WGS_MAX)
+        return fail(UTM_EINVAL, "target_wgs %d: 0 (the rule) or 1 .. %d", target_wgs, UTM_LIST_TARGET_WGS_MAX);
+    c->list_shape_lanes = lanes;                    // (from the next build: a list in use keeps the form it was built for)
+    c->list_shape_target = (unsigned)target_wgs;    // (from the next launch)
+    return UTM_OK;
+}
+
+extern "C" int utm_get_list_shape(utm_ctx *c, int32_t *lanes, int32_t *wgs, int32_t *n)
+{
+    CTX(c);
+    if (!lanes || !wgs || !n) return fail(UTM_EINVAL, "an output pointer is NULL");
+    *n = (int32_t)std::min<i64>(UTM_LIST_LOG, c->list_builds);
+    for (int k = 0; k < UTM_LIST_LOG; ++k) {
+        lanes[k] = k < *n ? c->list_log_lanes[k] : 0;
+        wgs[k] = k < *n ? c->list_log_wgs[k] : 0;
+    }
     return UTM_OK;
 }
 

@@ -74,24 +74,33 @@ static void launch_score_list(utm_ctx *c, const Chunk &ch, unsigned a_ub, const 
 {
     const ListView &lv = ch.lv;
     const ScoreView v = score_view(ch);
-    const unsigned group = (unsigned)list_group(a_ub, lv.n_tiles);
+    const int lanes = lv.lanes;  // (decided at the build: 16 only for the tiles that have the form)
+    const unsigned group = (unsigned)list_group(a_ub, lv.n_tiles, 4 * (64 / lanes), list_target_wgs(lanes, c->list_shape_target));
     const unsigned n_groups = (a_ub + group - 1) / group;
     const unsigned blocks = (unsigned)round_up((u64)lv.n_tiles * n_groups, 8);  // XCD-aware map: tile_of_block()
+    if (lv.log_slot >= 0 && !c->list_log_wgs[lv.log_slot])  // (the build's first launch: utm_get_list_shape)
+        c->list_log_wgs[lv.log_slot] = (int)(lv.n_tiles * n_groups);
     const PickArgs pa = pick_args(c);
     LaunchTimer t(c);
-#define UTM_LAUNCH_LIST_K(T, FUSED)                                                                                                  \
-    UTM_TIMED_LAUNCH(t, (k_score_list<T, FUSED>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), (const v4u *)lv.entries,             \
+#define UTM_LAUNCH_LIST_K(T, FUSED, L)                                                                                               \
+    UTM_TIMED_LAUNCH(t, (k_score_list<T, FUSED, L>), dim3(blocks + (FUSED ? 1u : 0u)), dim3(256), (const v4u *)lv.entries,          \
                      (const unsigned *)lv.offs, c->n_local, v.cols, v.covered, v.wp, pending_of(c, ch, true), (const IterState *)c->d_st, \
                      (const unsigned *)c->d_act, c->d_cnt, group, n_groups, how.by_pos ? 1u : 0u, pa)
-#define UTM_LAUNCH_LIST(T)                          \
-    if (how.fused == 2) UTM_LAUNCH_LIST_K(T, 2);    \
-    else if (how.fused == 1) UTM_LAUNCH_LIST_K(T, 1); \
-    else UTM_LAUNCH_LIST_K(T, 0)
+#define UTM_LAUNCH_LIST(T, L)                          \
+    if (how.fused == 2) UTM_LAUNCH_LIST_K(T, 2, L);    \
+    else if (how.fused == 1) UTM_LAUNCH_LIST_K(T, 1, L); \
+    else UTM_LAUNCH_LIST_K(T, 0, L)
     switch (lv.t) {
-    case UTM_LIST_T_TEST: UTM_LAUNCH_LIST(UTM_LIST_T_TEST); break;
-    case 16: UTM_LAUNCH_LIST(16); break;
-    case 18: UTM_LAUNCH_LIST(18); break;
-    default: UTM_LAUNCH_LIST(20); break;
+    case UTM_LIST_T_TEST:
+        if (lanes == 16) { UTM_LAUNCH_LIST(UTM_LIST_T_TEST, 16); }
+        else { UTM_LAUNCH_LIST(UTM_LIST_T_TEST, 64); }
+        break;
+    case 16:
+        if (lanes == 16) { UTM_LAUNCH_LIST(16, 16); }
+        else { UTM_LAUNCH_LIST(16, 64); }
+        break;
+    case 18: UTM_LAUNCH_LIST(18, 64); break;
+    default: UTM_LAUNCH_LIST(20, 64); break;
     }
 #undef UTM_LAUNCH_LIST
 #undef UTM_LAUNCH_LIST_K

@@ -78,6 +78,12 @@ __global__ __launch_bounds__(256) void k_list_fill(const u64 *__restrict__ cols,
 // tile in LDS (group 0 stores the ORed words, as k_score_int does); each wave then streams whole segments with 16-byte
 // loads, UTM_LIST_U of them in flight, and for every entry reads one LDS word and tests one bit.  A wave reduction and
 // one atomic per (position, tile).  The pick (fused_pick / k_pick) does not know the difference.
+//
+// L = lanes that share one segment.  64: the form above.  16 (list_score_rows): for builds of short segments a wave takes
+// four consecutive positions of act[] per round, one per DPP row of 16 lanes, so a workgroup takes 16; the batch loop runs
+// to the longest of the wave's four segments (a row past its end reads the sentinel quad), the reduction stops at the
+// row (row_shr 1 / 2 / 4 / 8 leave a row's sum in its lane 15) and lanes 15, 31, 47, 63 issue the four atomics in one
+// instruction.  Same layout, same arrivals, same bytes: the host chooses by the build's mean segment (list_lanes).
 // ------------------------------------------------------------------------------------------------
 #define UTM_LIST_U 4
 template <int T>
@@ -87,7 +93,69 @@ __device__ __forceinline__ unsigned list_live_bits(const unsigned *live, const v
            ((live[e.w >> 5] >> (e.w & 31)) & 1u);
 }
 
+// The row form's loop (L = 16), after the kernel's common head: see k_score_list.  i, s, q0 .. are per lane and equal
+// over a row; `ib`, the position of the wave's row 0, is what the wave's control flow goes by.
+#define UTM_LIST_ROW_U 4  // 16-byte loads per lane in flight, as UTM_LIST_U: a row's batch is 64 quads
 template <int T, int FUSED>
+__device__ __forceinline__ void list_score_rows(const v4u *__restrict__ entries, const unsigned *__restrict__ so, unsigned stride,
+                                                const unsigned *__restrict__ act, u64 *__restrict__ cnt, const unsigned *live,
+                                                unsigned lo, unsigned hi, unsigned ib, unsigned i, unsigned s, unsigned s_next,
+                                                unsigned s_next2, unsigned by_pos, const PickArgs &pa, v4u (&x)[UTM_LIST_ROW_U],
+                                                unsigned q0, unsigned q1, unsigned nq0, unsigned nq1)
+{
+    const unsigned r = threadIdx.x & 15;
+    const v4u sent4 = {1u << T, 1u << T, 1u << T, 1u << T};
+    while (ib < hi) {  // (uniform over the wave: row 0 holds its lowest position)
+        unsigned acc = 0;
+        if (__builtin_amdgcn_ballot_w64(q0 < q1) != 0) {  // (all four segments empty: nothing but the arrivals)
+#pragma unroll
+            for (int u = 0; u < UTM_LIST_ROW_U; ++u) acc += list_live_bits<T>(live, x[u]);  // the first batch is in flight already
+#pragma unroll 1
+            for (unsigned qb = q0 + 16 * UTM_LIST_ROW_U; __builtin_amdgcn_ballot_w64(qb < q1) != 0; qb += 16 * UTM_LIST_ROW_U) {
+                // (to the end of the longest of the four segments: a row past its own reads the sentinel quad)
+#pragma unroll
+                for (int u = 0; u < UTM_LIST_ROW_U; ++u) {
+                    const unsigned q = qb + u * 16 + r;
+                    x[u] = q < q1 ? entries[q] : sent4;
+                }
+#pragma unroll
+                for (int u = 0; u < UTM_LIST_ROW_U; ++u) acc += list_live_bits<T>(live, x[u]);
+            }
+        }
+        const unsigned done_i = i, done_s = s;
+        ib += 16;
+        i += 16;
+        s = s_next;
+        s_next = s_next2;
+        q0 = i < hi ? nq0 : 0u;  // (a row at or past hi has no segment: it loads nothing and adds nothing)
+        q1 = i < hi ? nq1 : 0u;
+        if (ib < hi) {
+            // the successor round's first batch, its successor's offsets and the index behind that: before the reduction and the atomics
+#pragma unroll
+            for (int u = 0; u < UTM_LIST_ROW_U; ++u) {
+                const unsigned q = q0 + u * 16 + r;
+                x[u] = q < q1 ? entries[q] : sent4;
+            }
+            if (s_next >= stride) s_next = 0;  // (never: act[] holds local samples; checked here, a round after its load was issued)
+            nq0 = so[s_next];
+            nq1 = so[s_next + 1];
+            s_next2 = i + 32 < hi ? act[i + 32] : 0;
+        }
+        acc += (unsigned)__builtin_amdgcn_update_dpp(0, (int)acc, 0x111, 0xf, 0xf, true);  // row_shr:1
+        acc += (unsigned)__builtin_amdgcn_update_dpp(0, (int)acc, 0x112, 0xf, 0xf, true);  // row_shr:2
+        acc += (unsigned)__builtin_amdgcn_update_dpp(0, (int)acc, 0x114, 0xf, 0xf, true);  // row_shr:4
+        acc += (unsigned)__builtin_amdgcn_update_dpp(0, (int)acc, 0x118, 0xf, 0xf, true);  // row_shr:8 -> lane 15 of the row
+        const bool mine = r == 15 && done_i < hi;
+        if (FUSED) {
+            const bool drop = pa.test_drop && blockIdx.x == 0 && done_i == lo;  // (test hook: see PickArgs::test_drop)
+            if (mine && !drop) atomicAdd(&cnt[done_i], (u64)acc + (1ull << UTM_ARRIVAL_SHIFT));
+        } else if (mine && acc) {
+            atomicAdd(&cnt[by_pos ? done_i : done_s], (u64)acc);
+        }
+    }
+}
+
+template <int T, int FUSED, int L>
 __global__ __launch_bounds__(256) void k_score_list(const v4u *__restrict__ entries, const unsigned *__restrict__ seg_off, unsigned stride,
                                                     const u64 *__restrict__ cols, u64 *__restrict__ covered, u64 wp, const Pending pend,
                                                     const IterState *__restrict__ st, const unsigned *__restrict__ act, u64 *__restrict__ cnt,
@@ -98,17 +166,21 @@ __global__ __launch_bounds__(256) void k_score_list(const v4u *__restrict__ entr
     __shared__ v4u live4[LIVE_Q + 1];                // ... + the sentinel's word (and three more), always zero
     __shared__ IntCand pick_lds[5];
     const unsigned *live = reinterpret_cast<const unsigned *>(live4);
+    static_assert(L == 64 || L == 16, "a segment is shared by a wave or by a DPP row");
+    constexpr unsigned STEP = 4 * (64 / L);  // positions of act[] a workgroup takes per round: between a wave's (row's) segments
+    static_assert(2 * STEP + 16 <= UTM_PICK_PAD, "the read-ahead of act[] stays inside its padding");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned tile, grp;
     const bool has_unit = tile_of_block(wp, TILE_WORDS, n_groups, tile, grp);
     const unsigned lo = grp * group_size;
-    unsigned i = lo + wave;
+    const unsigned ib = L == 64 ? lo + wave : lo + wave * 4;  // the wave's (its row 0's) first position
+    unsigned i = L == 64 ? ib : ib + (lane >> 4);
     // this wave's first three entries of act[], read ahead of the bounds that say whether they count (act[] is padded and
     // holds sample indices throughout, so the offsets read for them are inside the table too)
-    const bool in_act = has_unit && i + 8 < pa.n_local + UTM_PICK_PAD;
+    const bool in_act = has_unit && i + 2 * STEP < pa.n_local + UTM_PICK_PAD;
     unsigned s = in_act ? act[i] : 0;
-    unsigned s_next = in_act ? act[i + 4] : 0;
-    unsigned s_next2 = in_act ? act[i + 8] : 0;
+    unsigned s_next = in_act ? act[i + STEP] : 0;
+    unsigned s_next2 = in_act ? act[i + 2 * STEP] : 0;
     typedef unsigned v8u __attribute__((ext_vector_type(8)));
     v8u raw;
     asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(raw) : "s"(st) : "memory");
@@ -132,12 +204,21 @@ __global__ __launch_bounds__(256) void k_score_list(const v4u *__restrict__ entr
     unsigned q0 = so[s], q1 = so[s + 1];
     unsigned nq0 = so[s_next], nq1 = so[s_next + 1];
     const v4u sent4 = {1u << T, 1u << T, 1u << T, 1u << T};
-    v4u x[UTM_LIST_U];
+    v4u x[L == 64 ? UTM_LIST_U : UTM_LIST_ROW_U];
     // the first batch of this wave's first segment is requested before the tile is staged
-    if (i < hi) {
+    if constexpr (L == 64) {
+        if (i < hi) {
 #pragma unroll
-        for (int u = 0; u < UTM_LIST_U; ++u) {
-            const unsigned q = q0 + u * 64 + lane;
+            for (int u = 0; u < UTM_LIST_U; ++u) {
+                const unsigned q = q0 + u * 64 + lane;
+                x[u] = q < q1 ? entries[q] : sent4;
+            }
+        }
+    } else {
+        if (i >= hi) q0 = q1 = 0;  // (a row at or past hi has no segment)
+#pragma unroll
+        for (int u = 0; u < UTM_LIST_ROW_U; ++u) {  // (a wave past hi asks for nothing: q1 = 0 in all its rows)
+            const unsigned q = q0 + u * 16 + (lane & 15);
             x[u] = q < q1 ? entries[q] : sent4;
         }
     }
@@ -159,44 +240,48 @@ __global__ __launch_bounds__(256) void k_score_list(const v4u *__restrict__ entr
     }
     __syncthreads();
 
-    while (i < hi) {
-        unsigned acc = 0;
+    if constexpr (L == 16) {
+        list_score_rows<T, FUSED>(entries, so, stride, act, cnt, live, lo, hi, ib, i, s, s_next, s_next2, by_pos, pa, x, q0, q1, nq0, nq1);
+    } else {
+        while (i < hi) {
+            unsigned acc = 0;
 #pragma unroll 1
-        for (unsigned qb = q0; qb < q1; qb += 64 * UTM_LIST_U) {  // (uniform over the wave)
-            if (qb != q0) {
+            for (unsigned qb = q0; qb < q1; qb += 64 * UTM_LIST_U) {  // (uniform over the wave)
+                if (qb != q0) {
+#pragma unroll
+                    for (int u = 0; u < UTM_LIST_U; ++u) {
+                        const unsigned q = qb + u * 64 + lane;
+                        x[u] = q < q1 ? entries[q] : sent4;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < UTM_LIST_U; ++u) acc += list_live_bits<T>(live, x[u]);
+            }
+            const unsigned done_i = i, done_s = s;
+            i += 4;
+            s = s_next;
+            s_next = s_next2;
+            q0 = nq0;
+            q1 = nq1;
+            if (i < hi) {
+                // the successor's first batch, its successor's offsets and the index behind that: before the reduction and the atomic
 #pragma unroll
                 for (int u = 0; u < UTM_LIST_U; ++u) {
-                    const unsigned q = qb + u * 64 + lane;
+                    const unsigned q = q0 + u * 64 + lane;
                     x[u] = q < q1 ? entries[q] : sent4;
                 }
+                nq0 = so[s_next];
+                nq1 = so[s_next + 1];
+                s_next2 = i + 8 < hi ? act[i + 8] : 0;
+                if (s_next2 >= stride) s_next2 = 0;
             }
-#pragma unroll
-            for (int u = 0; u < UTM_LIST_U; ++u) acc += list_live_bits<T>(live, x[u]);
-        }
-        const unsigned done_i = i, done_s = s;
-        i += 4;
-        s = s_next;
-        s_next = s_next2;
-        q0 = nq0;
-        q1 = nq1;
-        if (i < hi) {
-            // the successor's first batch, its successor's offsets and the index behind that: before the reduction and the atomic
-#pragma unroll
-            for (int u = 0; u < UTM_LIST_U; ++u) {
-                const unsigned q = q0 + u * 64 + lane;
-                x[u] = q < q1 ? entries[q] : sent4;
+            acc = wave_sum_u32(acc);
+            if (FUSED) {
+                const bool drop = pa.test_drop && blockIdx.x == 0 && done_i == lo;  // (test hook: see PickArgs::test_drop)
+                if (lane == 0 && !drop) atomicAdd(&cnt[done_i], (u64)acc + (1ull << UTM_ARRIVAL_SHIFT));
+            } else if (lane == 0 && acc) {
+                atomicAdd(&cnt[by_pos ? done_i : done_s], (u64)acc);
             }
-            nq0 = so[s_next];
-            nq1 = so[s_next + 1];
-            s_next2 = i + 8 < hi ? act[i + 8] : 0;
-            if (s_next2 >= stride) s_next2 = 0;
-        }
-        acc = wave_sum_u32(acc);
-        if (FUSED) {
-            const bool drop = pa.test_drop && blockIdx.x == 0 && done_i == lo;  // (test hook: see PickArgs::test_drop)
-            if (lane == 0 && !drop) atomicAdd(&cnt[done_i], (u64)acc + (1ull << UTM_ARRIVAL_SHIFT));
-        } else if (lane == 0 && acc) {
-            atomicAdd(&cnt[by_pos ? done_i : done_s], (u64)acc);
         }
     }
 }

@@ -14,6 +14,9 @@
 #define UTM_LIST_MAX_TILES 48     // tiles per column the rule aims below: one atomic per (position, tile) on a count word
 #define UTM_LIST_TARGET_WGS 1024  // workgroups of a list launch: the device about twice over (256 CUs x 2)
 #define UTM_LIST_T_TEST 13        // the smallest tile (8,192 positions = one KiB of a column): tests only
+#define UTM_LIST_ROW_QUADS 64     // a build whose mean segment is at most this many quads is scored 16 lanes per segment
+#define UTM_LIST_TARGET_WGS_ROWS 2048  // workgroups of such a launch: 8 resident per CU at the 8 KiB mask (256 CUs x 8)
+#define UTM_LIST_TARGET_WGS_MAX 65536  // the largest target utm_set_list_shape takes
 
 static inline uint64_t list_sat_mul(uint64_t a, uint64_t b)
 {
@@ -54,12 +57,40 @@ static inline int list_tile_log2(uint64_t wp, int forced, uint64_t max_tiles)
     return list_tiles(wp, t) <= max_tiles ? t : 0;
 }
 
-// Positions of act[] per workgroup of a list launch: about UTM_LIST_TARGET_WGS workgroups, whole waves' worth (4).
-static inline uint64_t list_group(uint64_t a, uint64_t tiles)
+// Lanes of a wave that share one segment in the scoring launches of a build: 64 (a wave walks one segment at a time), or
+// 16 (one segment per DPP row, four positions of act[] per wave and round) when the build's mean segment -- `quads` over
+// `tiles` x `listed` segments -- is at most UTM_LIST_ROW_QUADS, one batch of a row.  Decided once per build.
+static inline int list_lanes(uint64_t quads, uint64_t tiles, uint64_t listed)
 {
-    uint64_t g = (list_sat_mul(a, tiles) + UTM_LIST_TARGET_WGS - 1) / UTM_LIST_TARGET_WGS;
-    g = (g + 3) / 4 * 4;
-    return g < 4 ? 4 : g;
+    const uint64_t segs = list_sat_mul(tiles, listed);
+    if (!segs) return 64;
+    return quads <= list_sat_mul(segs, UTM_LIST_ROW_QUADS) ? 16 : 64;
+}
+
+// The 16-lane form is built for the tiles whose builds have short segments (2^13, 2^16); any other tile keeps 64 lanes,
+// whatever the rule or utm_set_list_shape says.
+static inline int list_lanes_of_tile(int t, int lanes)
+{
+    return (lanes == 16 && (t == UTM_LIST_T_TEST || t == 16)) ? 16 : 64;
+}
+
+// Positions of act[] per workgroup of a list launch: about `target` workgroups over a x tiles units, in whole rounds of
+// `round` positions (4 waves x 64 / lanes: 4 or 16).
+static inline uint64_t list_group(uint64_t a, uint64_t tiles, uint64_t round, uint64_t target)
+{
+    if (!round) round = 4;
+    if (!target) target = 1;
+    const uint64_t units = list_sat_mul(a, tiles);
+    const uint64_t g = units / target + (units % target ? 1 : 0);
+    const uint64_t rounds = g / round + (g % round ? 1 : 0);
+    return list_sat_mul(rounds ? rounds : 1, round);
+}
+// ... and the target of a launch: the row form's own, the whole-wave form's as before; `forced` (utm_set_list_shape) > 0
+// replaces the row form's.
+static inline uint64_t list_target_wgs(int lanes, uint64_t forced)
+{
+    if (lanes != 16) return UTM_LIST_TARGET_WGS;
+    return forced ? forced : UTM_LIST_TARGET_WGS_ROWS;
 }
 
 // Exclusive scan of the padded counts (entries rounded up to whole quads of 4), in quads.  counts and offs hold n values

@@ -274,6 +274,9 @@ struct ListView {
     bool had = false;      // this run has had a list view of the chunk: every later compaction pass rebuilds it
     bool refused = false;  // a build did not fit: the chunk stays on its bitmap view for this run
     int t = 0;             // tiles of 2^t positions
+    int lanes = 64;        // lanes that share a segment in this build's scoring launches: list_lanes, or what was forced,
+                           // and 64 for a tile that has no 16-lane form -- decided once, at the build
+    int log_slot = -1;     // the build's place in the context's log (-1: past its end)
     unsigned n_tiles = 0;
     unsigned *entries = nullptr;  // quads of u32 entries, all segments back to back
     u64 cap_quads = 0;
@@ -470,6 +473,8 @@ struct utm_ctx {
     double list_ratio = UTM_LIST_RATIO;
     int list_test_t = 0;            // test hook: the tile of every build (0: the rule's)
     u64 list_test_cap = 0;          // test hook: a build of more padded entries than this is refused (0: no limit)
+    int list_shape_lanes = 0;       // utm_set_list_shape: lanes per segment of every build (0: list_lanes)
+    unsigned list_shape_target = 0; // ... and the workgroup target of the 16-lane launches (0: UTM_LIST_TARGET_WGS_ROWS)
     i64 list_builds = 0, list_refused = 0;  // since the last utm_reset
     i64 list_bytes = 0;
     double list_ms = 0.0;
@@ -478,6 +483,7 @@ struct utm_ctx {
     u64 list_log_entries[UTM_LIST_LOG] = {0}, list_log_padded[UTM_LIST_LOG] = {0};
     double list_log_ms[UTM_LIST_LOG] = {0};
     i64 list_log_bytes[UTM_LIST_LOG] = {0};
+    int list_log_lanes[UTM_LIST_LOG] = {0}, list_log_wgs[UTM_LIST_LOG] = {0};
 };
 
 // The loop scores the chunks themselves again; the views' buffers stay.  Only where the chunks' covered masks are current:

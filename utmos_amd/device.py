@@ -468,6 +468,18 @@ class DeviceMatrix:
                            padded=st.log_padded[k], ms=st.log_ms[k], bytes=st.log_bytes[k]) for k in range(min(16, st.builds))]
         return out
 
+    def set_list_shape(self, lanes=0, target_wgs=0):
+        """Lanes of a wave that share one list segment (16 or 64; 0 = by the build's mean segment) from the next build on,
+        and the workgroup target of the 16-lane launches (1 .. 65536; 0 = the library's) from the next launch.  Same rows."""
+        nat.check(nat.lib().utm_set_list_shape(self._h, int(lanes), int(target_wgs)))
+
+    def list_shape(self):
+        """[{"lanes", "wgs"}] of the first 16 list builds since the last reset, in the order of list_stats()["log"]: the lanes
+        per segment and the scoring workgroups of the build's first launch."""
+        lanes, wgs, n = (ctypes.c_int32 * 16)(), (ctypes.c_int32 * 16)(), ctypes.c_int32(0)
+        nat.check(nat.lib().utm_get_list_shape(self._h, lanes, wgs, ctypes.byref(n)))
+        return [dict(lanes=lanes[k], wgs=wgs[k]) for k in range(n.value)]
+
     def set_profile(self, on):
         nat.check(nat.lib().utm_set_profile(self._h, 1 if on else 0))
 
