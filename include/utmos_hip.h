@@ -752,6 +752,36 @@ int utm_vcf_timing(utm_vcf *vcf, double *ms);
 int utm_vcf_parse_bgzf(utm_vcf *vcf, const uint8_t *prefix, uint64_t prefix_bytes, const uint8_t *packed,
                        uint64_t packed_bytes, const uint32_t *members, uint64_t n_members, uint32_t flags,
                        uint64_t *n_records, uint64_t *carry_bytes);
+/* BCF2 batches on the same context: the genotype half of the reference's `convert` (utmos/convert.py:43-88) for the
+ * records of a BCF stream (DESIGN §8.4 states the format subset; utmos_amd/bcfio.py restates the reader on the CPU).
+ * The caller reads the header (magic, l_text, the header text) and resolves gt_key, GT's index in the header
+ * dictionary.  The text of the batch is: the carry of the previous batch, then prefix[0, prefix_bytes) (the first
+ * batch: the stream bytes after the header that the caller already holds), then either n_members whole BGZF members
+ * (`packed`, `members` as in utm_vcf_parse_bgzf, inflated and checked on the device) or, with n_members = 0,
+ * packed[0, packed_bytes) as stream bytes the caller has inflated (`packed` may be the staging: no copy).  The device
+ * follows the records' length prefixes; *n_records whole records are parsed, and the bytes after the last of them
+ * (*carry_bytes: a prefix of fewer than 8 bytes, or a record that runs past the batch) stay on the device and open the
+ * next batch.  UTM_BGZF_FIRST starts a file (drops any carry); with UTM_BGZF_LAST a non-empty carry fails the call with
+ * UTM_EINVAL and "truncated record ...".  A bad member fails the call as in utm_vcf_parse_bgzf.  A bad record
+ * (l_shared below 24, an n_sample other than the context's, more than 4096 alt alleles, a FORMAT field that runs past
+ * l_indiv, an unknown type code, a GT field of a non-integer type, no GT field) fails its batch at utm_vcf_fetch with
+ * UTM_EINVAL and "record <i> of the batch: <reason>".  The context stays usable either way.  utm_vcf_fetch returns
+ * the same per-record outputs as for VCF (no record is ever flagged UTM_VCF_SKIPPED). */
+int utm_vcf_parse_bcf(utm_vcf *vcf, const uint8_t *prefix, uint64_t prefix_bytes, const uint8_t *packed,
+                      uint64_t packed_bytes, const uint32_t *members, uint64_t n_members, uint32_t gt_key,
+                      uint32_t flags, uint64_t *n_records, uint64_t *carry_bytes);
+/* The device's BCF record walk and genotype decode built for the CPU (utmos/convert.py:43-88 for BCF input, as
+ * utm_vcf_parse_bcf): stream[0, n_bytes) = the bytes after the header.  *n_records = whole records, *carry_bytes = the
+ * bytes after the last of them.  With every output NULL only these two are set; otherwise rows[n_records * ceil(S/8)],
+ * af, n_het, n_hom and flags receive what utm_vcf_fetch would return (max_records = their room), and a bad record
+ * fails the call with UTM_EINVAL and "record <i> of the batch: <reason>".  Needs no GPU. */
+int utm_bcf_parse_host(const uint8_t *stream, uint64_t n_bytes, uint32_t n_samples, uint32_t gt_key,
+                       uint64_t max_records, uint8_t *rows, double *af, uint32_t *n_het, uint32_t *n_hom,
+                       uint8_t *flags, uint64_t *n_records, uint64_t *carry_bytes);
+/* The kernel time of utm_vcf_timing (its ms[1]) in two parts, summed over the fetched batches: ms[0] finding the
+ * records (VCF: the newline count and scan; BCF: k_bcf_chain), ms[1] parsing them (VCF: the newline offsets and
+ * k_vcf_parse; BCF: k_bcf_parse). */
+int utm_vcf_kernel_timing(utm_vcf *vcf, double *ms);
 /* HIP-event time of the BGZF inflate kernels summed over the fetched batches (ms[0]). */
 int utm_vcf_inflate_timing(utm_vcf *vcf, double *ms);
 /* The device's BGZF member decoder built for the CPU: one whole member (gzip header to trailer) -> its text, at most

@@ -1,7 +1,7 @@
 """VCF ingest benchmark: the CPU reader (utmos_amd/vcfio.read_vcf) against the GPU reader (utmos_amd/vcfgpu.py) on one
 seeded synthetic call set, uncompressed and BGZF, end to end in the same process, with the GPU reader's phase split.
 
-    python tools/vcf_bench.py --out DIR [--records 200000] [--samples 2504] [--seed 1] [--device 0] [--inflate both]
+    python tools/vcf_bench.py --out DIR [--records 200000] [--samples 2504] [--seed 1] [--device 0] [--inflate both] [--bcf]
 
 Writes DIR/synth.vcf and DIR/synth.vcf.gz (BGZF, zlib level 1: inflate speed barely depends on the level), prints one
 JSON line and writes it to DIR/vcf_bench.json.  The call set: FORMAT GT, `a|b` / `a/b` diploid calls, about 10 % of
@@ -11,6 +11,10 @@ records multi-allelic (2-3 alt alleles), 1 % missing alleles.  Phases (seconds u
   h2d_ms, kernel_ms, d2h_ms   HIP-event time of the copies and of the four parse kernels, summed over the batches
   inflate_ms  HIP-event time of the BGZF inflate kernels (GPU inflation only)
 BGZF is read with GPU inflation (gpu_bgzf) and with host inflation (gpu_bgzf_host_inflate); --inflate picks one.
+--bcf writes the same call set as BCF too (DIR/synth.raw.bcf the bare stream, DIR/synth.bcf in BGZF; GT as int8 x 2) and
+reads it the same three ways (gpu_bcf_raw, gpu_bcf_bgzf, gpu_bcf_bgzf_host_inflate); every result must equal the plain
+VCF's.  kernel_ms = find_ms + parse_ms (HIP events around each): for BCF find_ms is k_bcf_chain and parse_ms is
+k_bcf_parse; for VCF find_ms is k_vcf_nl_count + k_vcf_nl_scan and parse_ms is k_vcf_nl_write + k_vcf_parse.
   total_s     the whole call, header to the assembled arrays
 The write phase (skip with --skip-write) writes the call set's `convert` part file (.jl, the GT/AF/samples/stats dict)
 from the GPU reader's result: joblib.dump(compress=5) (convert's host path), the same pickle deflated in independent
@@ -33,11 +37,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def synth_text(seed, n_rec, n_samp, block=5000):
-    """Yields the VCF text in pieces: header first, then `block` records at a time."""
+def synth_blocks(seed, n_rec, n_samp, block=5000):
+    """Yields the call set `block` records at a time: (first record, n_alt per record, cells (nb, n_samp, 4) as the VCF
+    characters `a`, separator, `b`, tab or newline)."""
     rng = np.random.default_rng(seed)
-    yield ("##fileformat=VCFv4.2\n##source=vcf_bench\n" + "\t".join(
-        ["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + [f"HG{i:05d}" for i in range(n_samp)]) + "\n").encode()
     for b0 in range(0, n_rec, block):
         nb = min(block, n_rec - b0)
         n_alt = np.where(rng.random(nb) < 0.1, rng.integers(2, 4, nb), 1)
@@ -52,24 +55,77 @@ def synth_text(seed, n_rec, n_samp, block=5000):
         cells[:, :, 1] = np.where(rng.random((nb, n_samp)) < 0.9, ord("|"), ord("/"))
         cells[:, :, 3] = ord("\t")
         cells[:, -1, 3] = ord("\n")
-        alts = {1: "C", 2: "C,G", 3: "C,G,T"}
-        parts = []
-        for i in range(nb):
-            parts.append(f"chr1\t{1000 + b0 + i}\t.\tA\t{alts[int(n_alt[i])]}\t.\tPASS\t.\tGT\t".encode())
-            parts.append(cells[i].tobytes())
-        yield b"".join(parts)
+        yield b0, n_alt, cells
 
 
-def write_inputs(out, seed, n_rec, n_samp):
+def header_text(n_samp, bcf=False):
+    meta = "##fileformat=VCFv4.2\n##source=vcf_bench\n"
+    if bcf:   # the lines a BCF header needs: the dictionary (PASS = 0, GT = 1) and the contig
+        meta += '##FILTER=<ID=PASS,Description="All filters passed">\n##contig=<ID=chr1>\n##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n'
+    return (meta + "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + [f"HG{i:05d}" for i in range(n_samp)]) + "\n").encode()
+
+
+ALTS = {1: "C", 2: "C,G", 3: "C,G,T"}
+
+
+def vcf_piece(b0, n_alt, cells):
+    parts = []
+    for i in range(len(n_alt)):
+        parts.append(f"chr1\t{1000 + b0 + i}\t.\tA\t{ALTS[int(n_alt[i])]}\t.\tPASS\t.\tGT\t".encode())
+        parts.append(cells[i].tobytes())
+    return b"".join(parts)
+
+
+def bcf_piece(b0, n_alt, cells):
+    """The same records as BCF: GT as int8 x 2 per sample, (allele + 1) << 1 | phased, `.` = 0."""
+    import struct
+    n_samp = cells.shape[1]
+    al = cells[:, :, (0, 2)].astype(np.int16) - 48
+    gt = np.where(al < 0, 0, (al + 1) << 1).astype(np.uint8)
+    gt[:, :, 1] |= (cells[:, :, 1] == ord("|")).astype(np.uint8)
+    parts = []
+    for i in range(len(n_alt)):
+        k = int(n_alt[i])
+        shared = struct.pack("<iiiIII", 0, 999 + b0 + i, 1, 0x7F800001, (1 + k) << 16, 1 << 24 | n_samp)
+        shared += b"\x07\x17A" + b"".join(b"\x17" + a.encode() for a in ALTS[k].split(",")) + b"\x11\x00"
+        parts.append(struct.pack("<II", len(shared), 3 + 2 * n_samp) + shared + b"\x11\x01\x21")
+        parts.append(gt[i].tobytes())
+    return b"".join(parts)
+
+
+def synth_text(seed, n_rec, n_samp, block=5000):
+    """Yields the VCF text in pieces: header first, then `block` records at a time."""
+    yield header_text(n_samp)
+    for b0, n_alt, cells in synth_blocks(seed, n_rec, n_samp, block):
+        yield vcf_piece(b0, n_alt, cells)
+
+
+def write_inputs(out, seed, n_rec, n_samp, bcf=False):
+    """-> paths {plain, bgzf[, bcf_raw, bcf_bgzf]} of the one call set, seconds."""
+    import struct
     from utmos_amd.vcfgpu import bgzf_compress
-    plain, bgz = os.path.join(out, "synth.vcf"), os.path.join(out, "synth.vcf.gz")
+    paths = {"plain": os.path.join(out, "synth.vcf"), "bgzf": os.path.join(out, "synth.vcf.gz")}
+    if bcf:
+        paths.update(bcf_raw=os.path.join(out, "synth.raw.bcf"), bcf_bgzf=os.path.join(out, "synth.bcf"))
     t0 = time.perf_counter()
-    with open(plain, "wb") as fp, open(bgz, "wb") as fz:
-        for piece in synth_text(seed, n_rec, n_samp):
-            fp.write(piece)
-            fz.write(bgzf_compress(piece, level=1)[:-28])   # (one end-of-file member, at the end)
-        fz.write(bgzf_compress(b"", level=1))
-    return plain, bgz, time.perf_counter() - t0
+    files = {k: open(p, "wb") for k, p in paths.items()}
+    try:
+        def put(text, stream):
+            files["plain"].write(text)
+            files["bgzf"].write(bgzf_compress(text, level=1)[:-28])   # (one end-of-file member, at the end)
+            if bcf:
+                files["bcf_raw"].write(stream)
+                files["bcf_bgzf"].write(bgzf_compress(stream, level=1)[:-28])
+        head = header_text(n_samp, bcf=True) + b"\0" if bcf else b""
+        put(header_text(n_samp), b"BCF\x02\x02" + struct.pack("<I", len(head)) + head)
+        for b0, n_alt, cells in synth_blocks(seed, n_rec, n_samp):
+            put(vcf_piece(b0, n_alt, cells), bcf_piece(b0, n_alt, cells) if bcf else b"")
+        for k in ("bgzf", "bcf_bgzf")[:2 if bcf else 1]:
+            files[k].write(bgzf_compress(b"", level=1))
+    finally:
+        for fh in files.values():
+            fh.close()
+    return paths, time.perf_counter() - t0
 
 
 def inflate_only(path, threads):
@@ -180,13 +236,16 @@ def main():
     ap.add_argument("--skip-cpu", action="store_true", help="GPU reader only (e.g. under a profiler)")
     ap.add_argument("--skip-write", action="store_true", help="no write phase")
     ap.add_argument("--write-only", action="store_true", help="the write phase alone (after one GPU read)")
+    ap.add_argument("--bcf", action="store_true",
+                    help="also write the call set as BCF (bare stream and BGZF) and read it through the GPU reader")
     ap.add_argument("--inflate", choices=["both", "gpu", "host"], default="both",
                     help="BGZF through the GPU reader with GPU inflation, host inflation, or both [both]")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     from utmos_amd import device, vcfgpu, vcfio
 
-    plain, bgz, gen_s = write_inputs(args.out, args.seed, args.records, args.samples)
+    paths, gen_s = write_inputs(args.out, args.seed, args.records, args.samples, args.bcf)
+    plain, bgz = paths["plain"], paths["bgzf"]
     text_bytes = os.path.getsize(plain)
     res = {"records": args.records, "samples": args.samples, "text_bytes": text_bytes, "bgzf_bytes": os.path.getsize(bgz),
            "generate_s": round(gen_s, 2), "inflate_threads": vcfgpu.inflate_threads()}
@@ -214,8 +273,21 @@ def main():
         with vcfgpu.GpuVcfReader(device=args.device, inflate=inflate) as reader:
             reader.read(os.path.join(ROOT, "tests", "golden", "vcf", "chunk0.vcf.gz"))  # warm-up: code objects, context
             gpu[form] = reader.read(path)
-            res[f"gpu_{form}"] = {k: round(v, 3) for k, v in reader.timing.items()}
+            res[f"gpu_{form}"] = {k: round(v, 3) for k, v in {**reader.timing, **reader.kernel_timing}.items()}
         assert same(gpu["plain"], gpu[form])
+    if args.bcf:   # the same calls as BCF: bare stream, BGZF inflated on the GPU, BGZF inflated on the host
+        res["bcf_bytes"], res["bcf_bgzf_bytes"] = os.path.getsize(paths["bcf_raw"]), os.path.getsize(paths["bcf_bgzf"])
+        for form, path, inflate in (("bcf_raw", paths["bcf_raw"], "auto"), ("bcf_bgzf", paths["bcf_bgzf"], "gpu"),
+                                    ("bcf_bgzf_host_inflate", paths["bcf_bgzf"], "host")):
+            with vcfgpu.GpuVcfReader(device=args.device, inflate=inflate) as reader:
+                reader.read(os.path.join(ROOT, "tests", "golden", "vcf", "chunk0.vcf.gz"))  # warm-up, as above
+                got = reader.read(path)
+                res[f"gpu_{form}"] = {k: round(v, 3) for k, v in {**reader.timing, **reader.kernel_timing}.items()}
+            assert same(gpu["plain"], got)
+            del got
+        for a, b in (("bcf_bgzf", "bgzf"), ("bcf_bgzf_host_inflate", "bgzf_host_inflate"), ("bcf_raw", "plain")):
+            if f"gpu_{b}" in res:
+                res[f"speedup_{a}_over_vcf_{b}"] = round(res[f"gpu_{b}"]["total_s"] / res[f"gpu_{a}"]["total_s"], 2)
     if "bgzf" not in gpu:
         gpu["bgzf"] = gpu["bgzf_host_inflate"]
     if "gpu_bgzf" in res:

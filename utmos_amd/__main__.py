@@ -2,7 +2,7 @@
 
 Commands: ``select`` (the MI355X greedy selection, same flags and output as the reference's
 ``utmos select``, utmos/__main__.py:17-47 dispatches it the same way), ``convert`` (a VCF's genotypes -> the
-reference's .jl part file, parsed on the GPU; utmos/convert.py) and ``version``.  ``select`` reads ``.vcf[.gz]``,
+reference's .jl part file, parsed on the GPU; utmos/convert.py) and ``version``.  ``select`` reads ``.vcf[.gz]``, ``.bcf``,
 ``.jl`` and ``.npz`` inputs directly.
 """
 import sys

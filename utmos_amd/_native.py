@@ -151,6 +151,9 @@ PROTOTYPES = {
     "utm_vcf_fetch": [_P, _P, _P, _P, _P, _P],
     "utm_vcf_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_vcf_parse_bgzf": [_P, _P, _U64, _P, _U64, _P, _U64, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
+    "utm_vcf_parse_bcf": [_P, _P, _U64, _P, _U64, _P, _U64, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
+    "utm_bcf_parse_host": [_P, _U64, _U32, _U32, _U64, _P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)],
+    "utm_vcf_kernel_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_vcf_inflate_timing": [_P, ctypes.POINTER(ctypes.c_double)],
     "utm_bgzf_inflate_host": [_P, _U64, _P, _U64, ctypes.POINTER(_U32)],
     "utm_deflate_bound": [_U64, ctypes.POINTER(_U64)],

@@ -1,4 +1,4 @@
-"""`convert`: a VCF's genotypes -> the reference's lightweight part file (utmos/convert.py), parsed on the GPU.
+"""`convert`: a VCF's or BCF's genotypes -> the reference's lightweight part file (utmos/convert.py), parsed on the GPU.
 
 Output (utmos/convert.py:79-98): joblib.dump({"samples", "GT" (numpy.packbits rows), "AF" (n, 1) float64,
 "stats": {"num_het", "num_hom"}}, compress=L) -- what the reference's `select` loads with joblib.load.  An output
@@ -15,9 +15,9 @@ from .select import setup_logging
 
 def parse_args(args):
     """The reference's flags (utmos/convert.py:16-40) plus --device."""
-    parser = argparse.ArgumentParser(prog="convert", description="Convert a VCF's genotypes to a lightweight numpy part file (GPU parser).")
+    parser = argparse.ArgumentParser(prog="convert", description="Convert a VCF's or BCF's genotypes to a lightweight numpy part file (GPU parser).")
     parser.add_argument("in_file", type=str,
-                        help="Input VCF (.vcf, .vcf.gz; BGZF is inflated on the GPU unless --inflate host)")
+                        help="Input VCF or BCF (.vcf, .vcf.gz, .bcf; BGZF is inflated on the GPU unless --inflate host)")
     parser.add_argument("out_file", type=str, help="Output joblib (.jl), or .npz")
     parser.add_argument("--no-singleton", action="store_true", help="Remove singleton variants")
     parser.add_argument("--lowmem", action="store_true",

@@ -48,6 +48,8 @@ struct utm_vcf : SlotPair<VcfSlot> {
     uint32_t row_bytes = 0;  // packed row: ceil(S / 8) bytes
     double ms[3] = {0, 0, 0};  // H2D, kernels, D2H
     double inflate_ms = 0;     // BGZF inflate kernels
+    double find_ms = 0;        // the two parts of ms[1]: finding the records (newline count + scan, or the BCF chain) ...
+    double parse_ms = 0;       // ... and parsing them (newline offsets + k_vcf_parse, or k_bcf_parse)
     u64 carry = 0;             // bytes at the head of slot[next]'s text that the next BGZF batch continues
     ~utm_vcf() { idle(device); }
 };
@@ -62,6 +64,14 @@ static const char *vcf_error_text(unsigned code)
     case VCF_E_NALT: return "more alt alleles than the parser holds (4096)";
     case VCF_E_HEADER: return "a #CHROM line after the first record";
     case VCF_E_RANGE: return "an allele number above 10^18";
+    case BCF_E_SHARED: return "l_shared below 24";
+    case BCF_E_TRUNC: return "the record runs past the end of its batch";
+    case BCF_E_NSAMPLE: return "a record whose n_sample differs from the header's sample count";
+    case BCF_E_NALT: return "more alt alleles than the parser holds (4096)";
+    case BCF_E_FIELD: return "a FORMAT field that runs past l_indiv";
+    case BCF_E_TYPE: return "an unknown type code";
+    case BCF_E_GT_TYPE: return "a GT field that is not of an integer type";
+    case BCF_E_NO_GT: return "no GT among the FORMAT fields";
     default: return "unknown record error";
     }
 }
@@ -108,6 +118,9 @@ extern "C" int utm_vcf_create(int device, uint32_t n_samples, uint64_t batch_byt
     if (n_samples > 32768u * 8u)  // rows above 32 KiB of LDS ask for it explicitly
         HIP_TRY(hipFuncSetAttribute((const void *)k_vcf_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(((n_samples + 31) / 32) * sizeof(unsigned))));
+    if (n_samples > 32768u * 8u)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_bcf_parse, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(((n_samples + 31) / 32) * sizeof(unsigned))));
     std::unique_ptr<utm_vcf> p(new utm_vcf());
     p->device = device;
     p->n_samples = n_samples;
@@ -145,12 +158,10 @@ extern "C" int utm_vcf_staging(utm_vcf *p, uint64_t n_bytes, uint8_t **buf, uint
     return UTM_OK;
 }
 
-// The end of both parse calls, once the text of m bytes and its newline counts per block are on the device: the
-// records are parsed and copied back, and the batch is queued.
-static int vcf_parse_records(utm_vcf *p, VcfSlot *s, u64 m, u64 n_blk, u64 n_rec)
+// Room for the results of n_rec records on the device and in pinned memory.
+static int vcf_reserve_results(utm_vcf *p, VcfSlot *s, u64 n_rec)
 {
     const u64 floor = 1024;
-    TRY(s->d_nl.reserve(n_rec, floor));
     TRY(s->d_rows.reserve(n_rec * p->row_bytes, floor * p->row_bytes));
     TRY(s->d_het.reserve(n_rec, floor));
     TRY(s->d_hom.reserve(n_rec, floor));
@@ -161,13 +172,12 @@ static int vcf_parse_records(utm_vcf *p, VcfSlot *s, u64 m, u64 n_blk, u64 n_rec
     TRY(s->h_het.reserve(n_rec, floor));
     TRY(s->h_hom.reserve(n_rec, floor));
     TRY(s->h_status.reserve(n_rec, floor));
-    HIP_TRY(hipEventRecord(s->ev[3], s->stream));
-    if (n_rec) {
-        k_vcf_nl_write<<<(unsigned)n_blk, VCF_THREADS, 0, s->stream>>>(s->d_text, (unsigned)m, s->d_blk, s->d_nl);
-        k_vcf_parse<<<(unsigned)n_rec, VCF_THREADS, p->row_words * sizeof(unsigned), s->stream>>>(
-            s->d_text, s->d_nl, p->n_samples, p->row_words, p->row_bytes, s->d_rows, s->d_af, s->d_het, s->d_hom, s->d_status, s->d_misc);
-        HIP_TRY(hipGetLastError());
-    }
+    return UTM_OK;
+}
+
+// The parse kernels are queued (between ev[3] and ev[4]): the results are copied back and the batch is queued.
+static int vcf_results_back(utm_vcf *p, VcfSlot *s, u64 n_rec)
+{
     HIP_TRY(hipEventRecord(s->ev[4], s->stream));
     if (n_rec) {
         HIP_TRY(hipMemcpyAsync(s->h_rows, s->d_rows, n_rec * p->row_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -181,6 +191,36 @@ static int vcf_parse_records(utm_vcf *p, VcfSlot *s, u64 m, u64 n_blk, u64 n_rec
     s->n_rec = n_rec;
     p->queued();
     return UTM_OK;
+}
+
+// The end of both VCF parse calls, once the text of m bytes and its newline counts per block are on the device: the
+// records are parsed and copied back, and the batch is queued.
+static int vcf_parse_records(utm_vcf *p, VcfSlot *s, u64 m, u64 n_blk, u64 n_rec)
+{
+    TRY(s->d_nl.reserve(n_rec, 1024));
+    TRY(vcf_reserve_results(p, s, n_rec));
+    HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+    if (n_rec) {
+        k_vcf_nl_write<<<(unsigned)n_blk, VCF_THREADS, 0, s->stream>>>(s->d_text, (unsigned)m, s->d_blk, s->d_nl);
+        k_vcf_parse<<<(unsigned)n_rec, VCF_THREADS, p->row_words * sizeof(unsigned), s->stream>>>(
+            s->d_text, s->d_nl, p->n_samples, p->row_words, p->row_bytes, s->d_rows, s->d_af, s->d_het, s->d_hom, s->d_status, s->d_misc);
+        HIP_TRY(hipGetLastError());
+    }
+    return vcf_results_back(p, s, n_rec);
+}
+
+// ... and of the BCF parse call: the record offsets of k_bcf_chain are in d_nl.
+static int bcf_parse_records(utm_vcf *p, VcfSlot *s, u64 n, u64 n_rec, unsigned gt_key)
+{
+    TRY(vcf_reserve_results(p, s, n_rec));
+    HIP_TRY(hipEventRecord(s->ev[3], s->stream));
+    if (n_rec) {
+        k_bcf_parse<<<(unsigned)n_rec, VCF_THREADS, p->row_words * sizeof(unsigned), s->stream>>>(
+            s->d_text, s->d_nl, (unsigned)n, p->n_samples, p->row_words, p->row_bytes, gt_key, s->d_rows, s->d_af, s->d_het, s->d_hom,
+            s->d_status, s->d_misc);
+        HIP_TRY(hipGetLastError());
+    }
+    return vcf_results_back(p, s, n_rec);
 }
 
 extern "C" int utm_vcf_parse(utm_vcf *p, const uint8_t *text, uint64_t n_bytes, uint64_t *n_records)
@@ -228,8 +268,9 @@ extern "C" int utm_vcf_fetch(utm_vcf *p, uint8_t *rows, double *af, uint32_t *n_
     } else {
         TRY(add_elapsed(&p->ms[0], s->ev[0], s->ev[1]));
     }
-    TRY(add_elapsed(&p->ms[1], s->ev[1], s->ev[2]));
-    TRY(add_elapsed(&p->ms[1], s->ev[3], s->ev[4]));
+    TRY(add_elapsed(&p->find_ms, s->ev[1], s->ev[2]));
+    TRY(add_elapsed(&p->parse_ms, s->ev[3], s->ev[4]));
+    p->ms[1] = p->find_ms + p->parse_ms;
     TRY(add_elapsed(&p->ms[2], s->ev[4], s->ev[5]));
     const u64 n = s->n_rec;
     if (s->h_misc[1] != 0xFFFFFFFFu) {
@@ -253,6 +294,34 @@ extern "C" int utm_vcf_timing(utm_vcf *p, double *ms)
     return UTM_OK;
 }
 
+// The member table of a BGZF batch: compressed bytes back to back in the staging, text from *out on; *out = its end.
+static int vcf_member_table(VcfSlot *s, const uint32_t *members, u64 n_members, u64 packed_bytes, u64 *out)
+{
+    u64 in_off = 0;
+    for (u64 i = 0; i < n_members; ++i) {
+        const u64 in_size = members[2 * i], isize = members[2 * i + 1];
+        if (in_size > packed_bytes - in_off) return fail(UTM_EINVAL, "member %llu runs past the %llu compressed bytes", (unsigned long long)i, (unsigned long long)packed_bytes);
+        if (isize > INF_OUT_MAX) return fail(UTM_EINVAL, "member %llu of the batch: %s", (unsigned long long)i, inf_error_text(INF_E_ISIZE));
+        s->h_members[i] = InfMember{(unsigned)in_off, (unsigned)in_size, (unsigned)*out, (unsigned)isize};
+        in_off += in_size;
+        *out += isize;
+        if (*out + 1 > UTM_VCF_MAX_BATCH) return fail(UTM_EINVAL, "a batch of more than 2^32 - 64 text bytes");
+    }
+    if (in_off != packed_bytes) return fail(UTM_EINVAL, "the members hold %llu of the %llu compressed bytes", (unsigned long long)in_off, (unsigned long long)packed_bytes);
+    return UTM_OK;
+}
+
+// Member i of the batch failed on the device: its status word becomes the call's error.
+static int vcf_member_failure(VcfSlot *s, unsigned i)
+{
+    unsigned st = 0;
+    HIP_TRY(hipMemcpy(&st, s->d_mstat + i, sizeof st, hipMemcpyDeviceToHost));
+    const unsigned code = st & 255, got = st >> 8, isize = s->h_members[i].isize;
+    if (code == INF_E_LENGTH) return fail(UTM_EINVAL, "member %u of the batch: %u bytes inflated, ISIZE says %u", i, got, isize);
+    if (code == INF_E_OUTPUT) return fail(UTM_EINVAL, "member %u of the batch: more than %u bytes inflated, ISIZE says %u", i, isize, isize);
+    return fail(UTM_EINVAL, "member %u of the batch: %s", i, inf_error_text(code));
+}
+
 extern "C" int utm_vcf_parse_bgzf(utm_vcf *p, const uint8_t *prefix, uint64_t prefix_bytes, const uint8_t *packed,
                                   uint64_t packed_bytes, const uint32_t *members, uint64_t n_members, uint32_t flags,
                                   uint64_t *n_records, uint64_t *carry_bytes)
@@ -274,17 +343,8 @@ extern "C" int utm_vcf_parse_bgzf(utm_vcf *p, const uint8_t *prefix, uint64_t pr
     TRY(s->d_members.reserve(n_members, 1024));
     TRY(s->d_mstat.reserve(n_members, 1024));
     TRY(s->h_members.reserve(n_members, 1024));
-    u64 in_off = 0, out = carry + prefix_bytes;
-    for (u64 i = 0; i < n_members; ++i) {
-        const u64 in_size = members[2 * i], isize = members[2 * i + 1];
-        if (in_size > packed_bytes - in_off) return fail(UTM_EINVAL, "member %llu runs past the %llu compressed bytes", (unsigned long long)i, (unsigned long long)packed_bytes);
-        if (isize > INF_OUT_MAX) return fail(UTM_EINVAL, "member %llu of the batch: %s", (unsigned long long)i, inf_error_text(INF_E_ISIZE));
-        s->h_members[i] = InfMember{(unsigned)in_off, (unsigned)in_size, (unsigned)out, (unsigned)isize};
-        in_off += in_size;
-        out += isize;
-        if (out + 1 > UTM_VCF_MAX_BATCH) return fail(UTM_EINVAL, "a batch of more than 2^32 - 64 text bytes");
-    }
-    if (in_off != packed_bytes) return fail(UTM_EINVAL, "the members hold %llu of the %llu compressed bytes", (unsigned long long)in_off, (unsigned long long)packed_bytes);
+    u64 out = carry + prefix_bytes;
+    TRY(vcf_member_table(s, members, n_members, packed_bytes, &out));
     const u64 n = out, m = n + (last ? 1 : 0);  // m: the text the parser sees (the last batch: + '\n' or a 0)
     if (packed && packed != s->h_text && packed_bytes) {
         TRY(s->h_text.grow(packed_bytes));
@@ -317,15 +377,7 @@ extern "C" int utm_vcf_parse_bgzf(utm_vcf *p, const uint8_t *prefix, uint64_t pr
     HIP_TRY(hipEventRecord(s->ev[2], s->stream));
     HIP_TRY(hipMemcpyAsync(s->h_misc, s->d_misc, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));  // records, carry, the first failing member
-    if (s->h_misc[3] != 0xFFFFFFFFu) {
-        const unsigned i = s->h_misc[3];
-        unsigned st = 0;
-        HIP_TRY(hipMemcpy(&st, s->d_mstat + i, sizeof st, hipMemcpyDeviceToHost));
-        const unsigned code = st & 255, got = st >> 8, isize = s->h_members[i].isize;
-        if (code == INF_E_LENGTH) return fail(UTM_EINVAL, "member %u of the batch: %u bytes inflated, ISIZE says %u", i, got, isize);
-        if (code == INF_E_OUTPUT) return fail(UTM_EINVAL, "member %u of the batch: more than %u bytes inflated, ISIZE says %u", i, isize, isize);
-        return fail(UTM_EINVAL, "member %u of the batch: %s", i, inf_error_text(code));
-    }
+    if (s->h_misc[3] != 0xFFFFFFFFu) return vcf_member_failure(s, s->h_misc[3]);
     const u64 n_rec = m ? s->h_misc[0] : 0, cut = s->h_misc[2];
     const u64 carry_next = last ? 0 : m - cut;
     if (carry_next) {  // the unfinished record: to the head of the other slot's text, on that slot's stream
@@ -341,6 +393,14 @@ extern "C" int utm_vcf_parse_bgzf(utm_vcf *p, const uint8_t *prefix, uint64_t pr
     p->carry = carry_next;
     *n_records = n_rec;
     *carry_bytes = carry_next;
+    return UTM_OK;
+}
+
+extern "C" int utm_vcf_kernel_timing(utm_vcf *p, double *ms)
+{
+    if (!p || !ms) return fail(UTM_EINVAL, "vcf or ms is NULL");
+    ms[0] = p->find_ms;
+    ms[1] = p->parse_ms;
     return UTM_OK;
 }
 

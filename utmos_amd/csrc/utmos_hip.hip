@@ -733,6 +733,7 @@ static int chunk_of(utm_ctx *c, int32_t chunk, Chunk **out)
 #include "host_shard.hip.h"
 #include "host_batch.hip.h"
 #include "host_vcf.hip.h"
+#include "host_bcf.hip.h"
 #include "host_deflate.hip.h"
 #include "host_h5.hip.h"
 #include "host_h5w.hip.h"

@@ -66,7 +66,7 @@ def resolve_given(names, given):
 
 def _build_parser():
     parser = argparse.ArgumentParser(prog="overlap", description="Count the variants every two samples share (MI355X).")
-    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm or .hdf5 store")
+    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .bcf, .jl, .npz parts, or one packed .utm or .hdf5 store")
     parser.add_argument("-o", "--out", type=str, default=None, metavar="FILE.npz",
                         help="write the whole matrix: shared (int64, n x n), samples, count, given, files (numpy .npz)")
     parser.add_argument("--pairs-out", type=str, default=None, metavar="FILE",
@@ -88,7 +88,7 @@ def _build_parser():
     gpu = parser.add_argument_group("GPU Arguments")
     gpu.add_argument("--device", type=int, default=0, help="GPU index [%(default)s]")
     gpu.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
-                     help="where BGZF (.vcf.gz from bgzip) input is inflated [%(default)s]")
+                     help="where BGZF (.vcf.gz from bgzip, .bcf) input is inflated [%(default)s]")
     return parser
 
 

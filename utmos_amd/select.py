@@ -369,8 +369,8 @@ def refined_selection(data, select_count=0.02, subset=None, exclude=None, includ
 # ---------------------------------------------------------------------------------------------- ingest
 def _read_part(path, dev=0, inflate="auto"):
     """One input file -> {'GT': packbits rows, 'AF': per-variant float64, 'samples'} (the reference's part dict).
-    VCFs are parsed on the run's GPU (vcfgpu.py); `inflate` says where BGZF is inflated."""
-    if path.endswith((".vcf.gz", ".vcf")):
+    VCFs and BCFs are parsed on the run's GPU (vcfgpu.py); `inflate` says where BGZF is inflated."""
+    if path.endswith((".vcf.gz", ".vcf", ".bcf")):
         from .vcfgpu import read_vcf
         try:
             return read_vcf(path, device=dev, inflate=inflate)
@@ -383,7 +383,7 @@ def _read_part(path, dev=0, inflate="auto"):
     if path.endswith(".npz"):
         with np.load(path, allow_pickle=False) as z:
             return {"GT": z["GT"], "AF": z["AF"], "samples": z["samples"]}
-    logging.error("%s: unknown file type (expected .vcf, .vcf.gz, .jl, .npz or a %s store)", path, STORE_SUFFIX)
+    logging.error("%s: unknown file type (expected .vcf, .vcf.gz, .bcf, .jl, .npz or a %s store)", path, STORE_SUFFIX)
     sys.exit(1)
 
 
@@ -676,7 +676,7 @@ def _build_parser():
     """The option surface of the reference's `utmos select` (flags, defaults and meaning: utmos/select.py:355-398),
     plus this build's --device / --brute-force / --exchange."""
     parser = argparse.ArgumentParser(prog="select", description="Select the fewest samples that capture the most variants (MI355X).")
-    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm or .hdf5 store")
+    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .bcf, .jl, .npz parts, or one packed .utm or .hdf5 store")
     parser.add_argument("-c", "--count", type=float, default=0.02,
                         help="how many samples: a fraction of all if < 1, a count if >= 1, every sample if -1 [%(default)s]")
     parser.add_argument("-o", "--out", type=str, default="/dev/stdout", help="TSV destination [stdout]")
@@ -761,7 +761,7 @@ def _build_parser():
     gpu.add_argument("--exchange", choices=["auto", "mailboxes", "rccl", "rccl-allreduce"], default="auto",
                      help="several processes: how the shards meet every iteration [auto: device mailboxes, else RCCL]")
     gpu.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
-                     help="where BGZF (.vcf.gz from bgzip) input is inflated: on the GPU (auto, gpu) or by host "
+                     help="where BGZF (.vcf.gz from bgzip, .bcf) input is inflated: on the GPU (auto, gpu) or by host "
                           "threads (host); gpu refuses gzip that is not BGZF [%(default)s]")
     return parser
 

@@ -85,7 +85,7 @@ def write_curve(fout, hist):
 def _build_parser():
     parser = argparse.ArgumentParser(prog="spectrum", description="Carrier-count histogram of the listed samples and the exact "
                                                                   "expected coverage of a random panel (MI355X).")
-    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm or .hdf5 store")
+    parser.add_argument("in_files", nargs="*", type=str, help="inputs: .vcf[.gz], .bcf, .jl, .npz parts, or one packed .utm or .hdf5 store")
     parser.add_argument("-o", "--out", type=str, default="/dev/stdout", metavar="FILE",
                         help="TSV of the histogram: carriers, variants, pct [stdout]")
     parser.add_argument("--curve-out", type=str, default=None, metavar="FILE",
@@ -111,7 +111,7 @@ def _build_parser():
     gpu = parser.add_argument_group("GPU Arguments")
     gpu.add_argument("--device", type=int, default=0, help="GPU index [%(default)s]")
     gpu.add_argument("--inflate", choices=["auto", "gpu", "host"], default="auto",
-                     help="where BGZF (.vcf.gz from bgzip) input is inflated [%(default)s]")
+                     help="where BGZF (.vcf.gz from bgzip, .bcf) input is inflated [%(default)s]")
     return parser
 
 

@@ -193,7 +193,7 @@ def refuse_several_processes(criteria):
 # ---------------------------------------------------------------------------------------------- the filter command
 def _build_parser():
     parser = argparse.ArgumentParser(prog="filter", description="Write the variants that pass the criteria, and all samples, as a .utm store (MI355X).")
-    parser.add_argument("in_files", nargs="+", type=str, help="inputs: .vcf[.gz], .jl, .npz parts, or one packed .utm or .hdf5 store")
+    parser.add_argument("in_files", nargs="+", type=str, help="inputs: .vcf[.gz], .bcf, .jl, .npz parts, or one packed .utm or .hdf5 store")
     parser.add_argument("-o", "--out", type=str, required=True, metavar="OUT.utm", help="the store to write")
     parser.add_argument("--kept-out", type=str, default=None, metavar="FILE.npz",
                         help="also write part, row (and af) of the kept variants in store order: the store itself forgets where its rows came from")

@@ -10,6 +10,12 @@ inflates BGZF members on a thread pool instead and cuts batches at newlines on t
 batch the host fills the other slot.  The kernels return per record the packed
 presence row, AF, het / hom-alt counts and the singleton flag of the reference's convert (utmos/convert.py:43-88).
 
+A ``.bcf`` path takes the BCF route (csrc/bcf.hip.h): the host reads the header -- inflating BGZF members
+until the magic, ``l_text`` and the header text are complete -- and resolves GT's dictionary index (bcfio.py); the rest
+of the stream goes to the device as whole BGZF members, or as stream bytes when the file is the bare stream or
+``inflate="host"``.  BCF has no newline, so the device also finds the records (by their length prefixes) and keeps the
+unfinished one between batches.  The result equals bcfio.read_bcf's.
+
 Contract: for every input on which vcfio.read_vcf succeeds and whose allele tokens are all ``.`` or unsigned decimals
 (below 10^18), GT, AF and samples are identical to read_vcf's.  A ``#CHROM`` line after the first record raises
 ValueError (read_vcf would restart its sample list), as does every input read_vcf rejects.
@@ -113,7 +119,8 @@ class _StreamSource:
 class _BgzfSource:
     """BGZF members inflated in parallel, each written to its place in the caller's buffer."""
 
-    def __init__(self, path, threads):
+    def __init__(self, path, threads, first=0):
+        """first: the member to start at (those in front of it are the caller's, e.g. a header it has read)."""
         self.path = path
         self.fh = open(path, "rb")
         self.mm = mmap.mmap(self.fh.fileno(), 0, access=mmap.ACCESS_READ)
@@ -123,7 +130,7 @@ class _BgzfSource:
             self.mm.close()
             self.fh.close()
             raise ValueError(f"{path}: {err}") from None
-        self.next = 0
+        self.next = first
         self.rest = b""  # inflated bytes that did not fit the last buffer
         self.pool = ThreadPoolExecutor(max_workers=threads or inflate_threads())
 
@@ -208,6 +215,7 @@ class GpuVcfReader:
         self.device, self.batch_bytes, self.threads, self.inflate = int(device), int(batch_bytes), threads, inflate
         self.handle, self.n_samples = None, None
         self.timing = {}
+        self.kernel_timing = {}
 
     def close(self):
         if self.handle is not None:
@@ -260,9 +268,12 @@ class GpuVcfReader:
     def read(self, path):
         """-> {'GT', 'AF' (n, 1), 'samples', 'stats': {'num_het', 'num_hom'}, 'singleton' (n,) bool}; self.timing holds
         the phase split of this call (seconds: fill = read / inflate on the host -- with BGZF inflated on the GPU, reading
-        the compressed bytes; ms: h2d, kernels, d2h, inflate = the GPU inflate kernels)."""
+        the compressed bytes; ms: h2d, kernels, d2h, inflate = the GPU inflate kernels).  self.kernel_timing splits kernel_ms into find_ms
+        (finding the records: newline count and scan, or k_bcf_chain) and parse_ms (parsing them)."""
         lib = nat.lib()
         t0 = time.perf_counter()
+        if path.endswith(".bcf"):
+            return self._read_bcf(path, t0)
         if path.endswith(".gz") and self.inflate != "host":
             with open(path, "rb") as fh:
                 bgzf = is_bgzf(fh.read(18))
@@ -333,65 +344,170 @@ class GpuVcfReader:
                 return self._no_samples(path, hs, samples, prefix)
             h = self._context(len(samples))
             width = (len(samples) + 7) // 8
-            table = np.array(members, dtype=np.int64).reshape(-1, 3)
-            off, size, isize = table[:, 0], table[:, 1], table[:, 2]
-            ends = np.cumsum(isize)
-
-            def batches(j, pre):
-                flags = BGZF_FIRST
-                while True:
-                    k = j
-                    if j < len(members):   # whole members, their text summed up to batch_bytes (at least one)
-                        base = ends[j - 1] if j else 0
-                        k = max(j + 1, int(np.searchsorted(ends, base + self.batch_bytes, side="right")))
-                    last = k == len(members)
-                    packed = int(off[k - 1] + size[k - 1] - off[j]) if k > j else 0
-                    tf = time.perf_counter()
-                    ptr, cap = ctypes.c_void_p(), ctypes.c_uint64()
-                    nat.check(lib.utm_vcf_staging(h, max(packed, 1), ctypes.byref(ptr), ctypes.byref(cap)))
-                    if packed:
-                        view = memoryview((ctypes.c_uint8 * packed).from_address(ptr.value)).cast("B")
-                        fh.seek(int(off[j]))
-                        got = 0
-                        while got < packed:
-                            n = fh.readinto(view[got:])
-                            if not n:
-                                raise ValueError(f"{path}: truncated")
-                            got += n
-                    mem = np.ascontiguousarray(np.stack([size[j:k], isize[j:k]], axis=1), dtype=np.uint32)
-                    fill = time.perf_counter() - tf
-                    n_rec, carry = ctypes.c_uint64(), ctypes.c_uint64()
-                    rc = lib.utm_vcf_parse_bgzf(h, pre.ctypes.data if pre is not None else None,
-                                                len(pre) if pre is not None else 0, ptr, packed, mem.ctypes.data,
-                                                k - j, flags | (BGZF_LAST if last else 0), ctypes.byref(n_rec),
-                                                ctypes.byref(carry))
-                    if rc == UTM_EINVAL:
-                        msg = lib.utm_last_error().decode("utf-8", "replace")
-                        m = re.match(r"member (\d+) of the batch: (.*)", msg)
-                        if m:
-                            msg = f"BGZF member at byte {int(off[j + int(m.group(1))])}: {m.group(2)}"
-                        raise ValueError(f"{path}: {msg}")
-                    nat.check(rc)
-                    yield n_rec.value, fill
-                    flags, pre, j = 0, None, k
-                    if last:
-                        return
-
-            pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
-            parts = self._pipeline(path, h, width, n_head, batches(hs.next, pre), t0)
+            batches = self._member_batches(path, fh, h, members, hs.next, prefix, lib.utm_vcf_parse_bgzf)
+            parts = self._pipeline(path, h, width, n_head, batches, t0)
         return self._assemble(parts, samples, width)
 
+    def _member_batches(self, path, fh, h, members, j, prefix, parse, *key):
+        """Whole BGZF members from member j on, read compressed into the staging in batches (ISIZE summed up to
+        batch_bytes, at least one member) and queued with `parse` (utm_vcf_parse_bgzf, or utm_vcf_parse_bcf with its
+        key); `prefix` = text the host already holds, in front of the first batch."""
+        lib = nat.lib()
+        table = np.array(members, dtype=np.int64).reshape(-1, 3)
+        off, size, isize = table[:, 0], table[:, 1], table[:, 2]
+        ends = np.cumsum(isize)
+        pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
+        flags, done = BGZF_FIRST, 0
+        while True:
+            k = j
+            if j < len(members):   # whole members, their text summed up to batch_bytes (at least one)
+                base = ends[j - 1] if j else 0
+                k = max(j + 1, int(np.searchsorted(ends, base + self.batch_bytes, side="right")))
+            last = k == len(members)
+            packed = int(off[k - 1] + size[k - 1] - off[j]) if k > j else 0
+            tf = time.perf_counter()
+            ptr, cap = ctypes.c_void_p(), ctypes.c_uint64()
+            nat.check(lib.utm_vcf_staging(h, max(packed, 1), ctypes.byref(ptr), ctypes.byref(cap)))
+            if packed:
+                view = memoryview((ctypes.c_uint8 * packed).from_address(ptr.value)).cast("B")
+                fh.seek(int(off[j]))
+                got = 0
+                while got < packed:
+                    n = fh.readinto(view[got:])
+                    if not n:
+                        raise ValueError(f"{path}: truncated")
+                    got += n
+            mem = np.ascontiguousarray(np.stack([size[j:k], isize[j:k]], axis=1), dtype=np.uint32)
+            fill = time.perf_counter() - tf
+            n_rec, carry = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = parse(h, pre.ctypes.data if pre is not None else None, len(pre) if pre is not None else 0, ptr, packed,
+                       mem.ctypes.data, k - j, *key, flags | (BGZF_LAST if last else 0), ctypes.byref(n_rec),
+                       ctypes.byref(carry))
+            if rc == UTM_EINVAL:
+                raise ValueError(f"{path}: {self._batch_error(done, lambda i: int(off[j + i]))}")
+            nat.check(rc)
+            yield n_rec.value, fill
+            flags, pre, j, done = 0, None, k, done + n_rec.value
+            if last:
+                return
+
+    @staticmethod
+    def _batch_error(done, member_at=None):
+        """utm_last_error() of a failed parse call, with the member's place in the file and the record's number in it
+        (`done` = records of the batches before)."""
+        msg = nat.lib().utm_last_error().decode("utf-8", "replace")
+        m = re.match(r"member (\d+) of the batch: (.*)", msg)
+        if m and member_at:
+            return f"BGZF member at byte {member_at(int(m.group(1)))}: {m.group(2)}"
+        m = re.match(r"record (\d+) of the batch: (.*)", msg)
+        if m:
+            return f"record {done + int(m.group(1)) + 1}: {m.group(2)}"
+        m = re.match(r"truncated record: the stream ends (\d+) bytes into record (\d+) of the batch", msg)
+        if m:
+            return f"record {done + int(m.group(2)) + 1}: truncated record (the file ends {m.group(1)} bytes into it)"
+        return msg
+
+    def _read_bcf(self, path, t0):
+        """A .bcf file: BGZF (members inflated on the GPU, or on the thread pool with inflate="host") or the bare
+        stream.  The host reads the header; the device finds and parses the records."""
+        from . import bcfio
+        lib = nat.lib()
+        if os.path.getsize(path) == 0:
+            raise ValueError(f"{path}: an empty file")
+        with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            head = bytes(mm[:18])
+            raw = head[:3] == bcfio.MAGIC[:3]
+            if not raw and not is_bgzf(head):
+                raise ValueError(f"{path}: neither a BCF stream (magic BCF\\x02) nor a BGZF container")
+            if raw:
+                members, src = None, _StreamSource(open(path, "rb", buffering=0))
+            else:
+                try:
+                    members = bgzf_members(mm)
+                except ValueError as err:
+                    raise ValueError(f"{path}: {err}") from None
+                src = _MemberSource(path, mm, members)
+            try:
+                samples, ids, prefix = bcfio.read_header(path, src.fill)
+                if len(samples) == 0:
+                    return self._no_samples_bcf(path, t0)
+                gt_key = ids.get("GT", bcfio.NO_KEY)
+                h = self._context(len(samples))
+                width = (len(samples) + 7) // 8
+                if members is not None and self.inflate != "host":
+                    batches = self._member_batches(path, fh, h, members, src.next, prefix + src.rest,
+                                                   lib.utm_vcf_parse_bcf, gt_key)
+                    parts = self._pipeline(path, h, width, None, batches, t0)
+                else:
+                    if members is not None:    # the members after the header's, inflated on the thread pool
+                        prefix, src = prefix + src.rest, _BgzfSource(path, self.threads, first=src.next)
+                    parts = self._pipeline(path, h, width, None, self._stream_batches(path, h, src, prefix, gt_key), t0)
+            finally:
+                src.close()
+        return self._assemble(parts, samples, width)
+
+    def _no_samples_bcf(self, path, t0):
+        """The header names no sample: there is no GT matrix and no parse context for it (utm_vcf_create wants a
+        sample).  The records are still checked -- each must say n_sample = 0 -- by bcfio on the host, which is the one
+        place a .bcf is not read on the GPU; self.timing says so with zero device times."""
+        from . import bcfio
+        t1 = time.perf_counter()
+        out = bcfio.read_bcf(path)
+        self.timing = {"fill_s": time.perf_counter() - t1, "h2d_ms": 0.0, "kernel_ms": 0.0,
+                       "d2h_ms": 0.0, "inflate_ms": 0.0, "total_s": time.perf_counter() - t0}
+        self.kernel_timing = {"find_ms": 0.0, "parse_ms": 0.0}
+        return out
+
+    def _stream_batches(self, path, h, src, prefix, gt_key):
+        """Stream bytes the host holds (the bare stream, or members it inflated), batch_bytes per batch."""
+        lib = nat.lib()
+        pre = np.frombuffer(prefix, dtype=np.uint8) if prefix else None
+        flags, done, eof = BGZF_FIRST, 0, False
+        while True:
+            tf = time.perf_counter()
+            ptr, cap = ctypes.c_void_p(), ctypes.c_uint64()
+            nat.check(lib.utm_vcf_staging(h, self.batch_bytes, ctypes.byref(ptr), ctypes.byref(cap)))
+            view = memoryview((ctypes.c_uint8 * self.batch_bytes).from_address(ptr.value)).cast("B")
+            n = 0
+            while n < self.batch_bytes and not eof:
+                k = src.fill(view[n:])
+                eof, n = k == 0, n + k
+            fill = time.perf_counter() - tf
+            n_rec, carry = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = lib.utm_vcf_parse_bcf(h, pre.ctypes.data if pre is not None else None, len(pre) if pre is not None else 0,
+                                       ptr, n, None, 0, gt_key, flags | (BGZF_LAST if eof else 0), ctypes.byref(n_rec),
+                                       ctypes.byref(carry))
+            if rc == UTM_EINVAL:
+                raise ValueError(f"{path}: {self._batch_error(done)}")
+            nat.check(rc)
+            yield n_rec.value, fill
+            flags, pre, done = 0, None, done + n_rec.value
+            if eof:
+                return
+
     def _pipeline(self, path, h, width, n_head, batches, t0):
-        """Runs the batches through the context's two slots -> the fetched parts, and sets self.timing.  `batches`
+        """Runs the batches through the context's two slots -> the fetched parts, and sets self.timing.  n_head = the
+        header's lines (errors name a line), or None for BCF (errors name a record, counted from the first).  `batches`
         stages and queues one batch per step and yields (its records, seconds spent filling its staging); it is
         resumed only once a slot is free for the next batch."""
         lib = nat.lib()
-        ms0, inf0 = (ctypes.c_double * 3)(), ctypes.c_double()
+        ms0, inf0, k0 = (ctypes.c_double * 3)(), ctypes.c_double(), (ctypes.c_double * 2)()
         nat.check(lib.utm_vcf_timing(h, ms0))
+        nat.check(lib.utm_vcf_kernel_timing(h, k0))
         nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf0)))
         pending, parts, line_base, fill_s = deque(), [], 0, 0.0
         try:
-            for n_rec, fill in batches:
+            it = iter(batches)
+            while True:
+                try:
+                    n_rec, fill = next(it)
+                except StopIteration:
+                    break
+                except ValueError:
+                    # a parse call failed: a batch queued before it may hold an earlier bad record, whose error comes first
+                    while pending:
+                        self._fetch(path, h, width, n_head, *pending.popleft())
+                    raise
                 pending.append((n_rec, line_base))
                 line_base += n_rec
                 fill_s += fill
@@ -403,9 +519,11 @@ class GpuVcfReader:
             while pending:                 # drain the other slot: the context stays usable after a failure
                 pending.popleft()
                 lib.utm_vcf_fetch(h, None, None, None, None, None)
-        ms1, inf1 = (ctypes.c_double * 3)(), ctypes.c_double()
+        ms1, inf1, k1 = (ctypes.c_double * 3)(), ctypes.c_double(), (ctypes.c_double * 2)()
         nat.check(lib.utm_vcf_timing(h, ms1))
+        nat.check(lib.utm_vcf_kernel_timing(h, k1))
         nat.check(lib.utm_vcf_inflate_timing(h, ctypes.byref(inf1)))
+        self.kernel_timing = {"find_ms": k1[0] - k0[0], "parse_ms": k1[1] - k0[1]}
         self.timing = {"fill_s": fill_s, "h2d_ms": ms1[0] - ms0[0], "kernel_ms": ms1[1] - ms0[1],
                        "d2h_ms": ms1[2] - ms0[2], "inflate_ms": inf1.value - inf0.value,
                        "total_s": time.perf_counter() - t0}
@@ -423,7 +541,8 @@ class GpuVcfReader:
             msg = nat.lib().utm_last_error().decode("utf-8", "replace")
             m = re.match(r"record (\d+) of the batch: (.*)", msg)
             if m:
-                msg = f"line {n_head + line_base + int(m.group(1)) + 1}: {m.group(2)}"
+                at = line_base + int(m.group(1)) + 1
+                msg = f"record {at}: {m.group(2)}" if n_head is None else f"line {n_head + at}: {m.group(2)}"
             raise ValueError(f"{path}: {msg}")
         nat.check(rc)
         keep = (flags & FLAG_SKIPPED) == 0
